@@ -6,7 +6,18 @@ resident in HBM, plus the per-step loss all-reduce of the data-parallel harness 
 rank renders its own view (independent views/timesteps shard across GPUs), so per-GPU
 work is fixed as N grows ("weak" scaling).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config metric] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config metric] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it uploads the scene, runs W untimed and K
+timed steps, writes the last step's outputs when --dump-outputs is given, and prints the result line.
+--full adds the other legs to that line, each of which takes runs of its own: per-stage and per-kernel
+hipEvent timings with the roofline figures, the train step (fp32, bf16 MLP, the reference's torch tail),
+the forward-only / autograd-wrapper / train-like-scene / other-config timings and the CPU baseline
+(--no-train-step, --no-extras and --no-cpu-baseline drop single legs of a --full run).
+
+--dump-outputs DIR writes what rank 0's last timed step returned to its caller as DIR/<name>.npy (float32):
+color, depth, radii, the L1 loss and the gradients of the inputs the step passes in.  The scene and the
+target image are seeded, so two builds run with the same arguments see identical inputs.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py launches its own N ranks
 (`torch.distributed.run`, 127.0.0.1) as a child process before anything touches the GPU, and exits
@@ -59,6 +70,11 @@ def parse_args(argv=None):
     ap.add_argument("--scene", default="synthetic", choices=["synthetic", "train_like"],
                     help="synthetic: the SURVEY §8d scene (the metric); train_like: make_train_like_scene "
                          "(profiling of the second workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: stage/kernel timings and roofline, train "
+                         "step, forward-only / autograd / train-like / other-config timings, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-train-step", action="store_true", help="skip the full train-step timing")
@@ -120,14 +136,40 @@ def main(argv=None):
     else:
         s = make_scene(P, W, H, seed=rank)
     scene = upload_scene(s, dev)
-    step = make_step(scene, dev, rank, dgr._C, dist)
+    last = {}
+    step = make_step(scene, dev, rank, dgr._C, dist, last)
     elapsed, nr = timed_steps(step, args.steps, args.warmup, dist)
     my_ms = elapsed / args.steps * 1e3
     per_rank = gather_per_rank([float(nr), my_ms], world, dev, dist)
     elapsed = max(r[1] for r in per_rank) * args.steps / 1e3   # max over ranks
     ms_per_step = elapsed / args.steps * 1e3
     value = world * P * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    last.clear()
 
+    out = {
+        "metric": BASELINE_METRIC,
+        "value": round(value, 3), "unit": "MGaussians/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic (seeded, SURVEY §8d)",
+        "config": {"workload": f"{args.config}: P={P} Gaussians, {W}x{H}, SH deg 3, 1 view/GPU/step, fwd+bwd",
+                   "global_batch": world, "parallelism": f"views x{world} (independent views + RCCL loss all-reduce)"},
+        "num_rendered": int(nr),
+        "per_rank": [{"rank": i, "num_rendered": int(r[0]), "ms_per_step": round(r[1], 4)}
+                     for i, r in enumerate(per_rank)],
+    }
+    if args.full:   # every rank runs the legs (the train step's collectives need all of them)
+        out.update(full_legs(args, s, scene, dgr, dev, world, rank, dist, P, W, H, int(nr), ms_per_step))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist:
+        tdist.destroy_process_group()
+
+
+def full_legs(args, s, scene, dgr, dev, world, rank, dist, P, W, H, L, ms_per_step):
+    """The legs of a --full run beyond the headline figure, as entries of the result line: stage and kernel
+    timings with the roofline figures, the train step, the extras and the CPU baseline."""
     stage_avg = stage_timings(scene, dgr._C, args.steps)
     kernel_avg = stage_timings(scene, dgr._C, args.steps, repeats=KERNEL_REPEATS)
 
@@ -142,56 +184,45 @@ def main(argv=None):
         extras["autograd_wrapper"] = autograd_timing(scene, dgr, args.steps, args.warmup, P)
         extras["train_like_scene"] = train_like_timing(P, W, H, dev, args.steps, args.warmup, dgr._C, rank)
         extras["configs"] = config_timings(dev, args.steps, args.warmup, dgr._C)
+    if rank != 0:
+        return {}
 
-    if rank == 0:
-        L = int(nr)
-        ab = algorithmic_bytes(P, L, W, H)
-        dom = max(stage_avg, key=stage_avg.get)
-        # the kernel's own duration: back-to-back launches between two events (agrees with rocprofv3's
-        # kernel-trace average; the per-stage brackets of stage_ms add their gaps)
-        dom_ms = kernel_avg.get(dom, stage_avg[dom])
-        dom_bytes = ab["render_backward"] if dom == "bwd.render_backward" else (
-            ab["render"] if dom == "fwd.render" else None)
-        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_bytes else None
-        prof = load_profile_summary(dom.split(".", 1)[1])
-        out = {
-            "metric": BASELINE_METRIC,
-            "value": round(value, 3), "unit": "MGaussians/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic (seeded, SURVEY §8d)",
-            "config": {"workload": f"{args.config}: P={P} Gaussians, {W}x{H}, SH deg 3, 1 view/GPU/step, fwd+bwd",
-                       "global_batch": world, "parallelism": f"views x{world} (independent views + RCCL loss all-reduce)"},
-            "num_rendered": L,
-            "per_rank": [{"rank": i, "num_rendered": int(r[0]), "ms_per_step": round(r[1], 4)}
-                         for i, r in enumerate(per_rank)],
-            "stage_ms": {k: round(v, 4) for k, v in stage_avg.items()},
-            "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2) if achieved else None,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
-                         "traffic": prof.get("traffic"), "traffic_raw": prof.get("traffic_raw"),
-                         "traffic_note": "PMC bytes per launch (profiles/pmc_traffic.json): traffic = 2 x FETCH_SIZE + "
-                                         "WRITE_SIZE (gfx950 wide-read correction), traffic_raw = FETCH_SIZE + "
-                                         "WRITE_SIZE; the kernel's reads are mostly gathers, so the truth lies between",
-                         "algorithmic_bytes": dom_bytes, "avg_ms": round(dom_ms, 4),
-                         "avg_ms_note": f"hipEvent average over {KERNEL_REPEATS} back-to-back launches on the "
-                                        f"launch stream; stage_ms (one launch per event bracket) reads "
-                                        f"{stage_avg[dom]:.4f}"},
-            "kernel_ms": {k: round(v, 4) for k, v in kernel_avg.items()},
-            "step_roofline": {"algorithmic_bytes": ab["step"],
-                              "achieved_GBs": round(ab["step"] / (ms_per_step * 1e-3) / 1e9, 2),
-                              "frac": round(ab["step"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
-        }
-        if prof.get("valu") is not None:
-            # the blend kernels are VALU-issue bound, not HBM bound: measured VALU busy fraction
-            out["valu_utilisation"] = prof["valu"]
-        out.update(extras)
-        if train is not None:
-            out["train_step"] = train
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(s, args.cpu_seconds)
-        print(json.dumps(out), flush=True)
-    if dist:
-        tdist.destroy_process_group()
+    ab = algorithmic_bytes(P, L, W, H)
+    dom = max(stage_avg, key=stage_avg.get)
+    # the kernel's own duration: back-to-back launches between two events (agrees with rocprofv3's
+    # kernel-trace average; the per-stage brackets of stage_ms add their gaps)
+    dom_ms = kernel_avg.get(dom, stage_avg[dom])
+    dom_bytes = ab["render_backward"] if dom == "bwd.render_backward" else (
+        ab["render"] if dom == "fwd.render" else None)
+    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_bytes else None
+    prof = load_profile_summary(dom.split(".", 1)[1])
+    out = {
+        "stage_ms": {k: round(v, 4) for k, v in stage_avg.items()},
+        "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2) if achieved else None,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
+                     "traffic": prof.get("traffic"), "traffic_raw": prof.get("traffic_raw"),
+                     "traffic_note": "PMC bytes per launch (profiles/pmc_traffic.json): traffic = 2 x FETCH_SIZE + "
+                                     "WRITE_SIZE (gfx950 wide-read correction), traffic_raw = FETCH_SIZE + "
+                                     "WRITE_SIZE; the kernel's reads are mostly gathers, so the truth lies between",
+                     "algorithmic_bytes": dom_bytes, "avg_ms": round(dom_ms, 4),
+                     "avg_ms_note": f"hipEvent average over {KERNEL_REPEATS} back-to-back launches on the "
+                                    f"launch stream; stage_ms (one launch per event bracket) reads "
+                                    f"{stage_avg[dom]:.4f}"},
+        "kernel_ms": {k: round(v, 4) for k, v in kernel_avg.items()},
+        "step_roofline": {"algorithmic_bytes": ab["step"],
+                          "achieved_GBs": round(ab["step"] / (ms_per_step * 1e-3) / 1e9, 2),
+                          "frac": round(ab["step"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
+    }
+    if prof.get("valu") is not None:
+        # the blend kernels are VALU-issue bound, not HBM bound: measured VALU busy fraction
+        out["valu_utilisation"] = prof["valu"]
+    out.update(extras)
+    if train is not None:
+        out["train_step"] = train
+    if not args.no_cpu_baseline and world == 1:
+        out["cpu_baseline"] = cpu_baseline(s, args.cpu_seconds)
+    return out
 
 
 def upload_scene(s, dev):
@@ -214,22 +245,53 @@ def _bwd(C, d, radii, grad, gb, nr, bb, ib):
                                           d["shs"], 3, d["campos"], gb, nr, bb, ib, False)
 
 
-def make_step(d, dev, seed, C, dist):
+def make_step(d, dev, seed, C, dist, last=None):
+    """The timed step.  With a dict `last`, each step leaves there what it returns to its caller (the previous
+    step's entries are dropped first, so no step allocates while an earlier step's outputs are alive)."""
     from gs4d_train import _C as TC
     gt = torch.tensor(np.random.default_rng(seed + 1).uniform(0, 1, (3, d["H"], d["W"])).astype(np.float32),
                       device=dev)
 
     def step():
+        if last is not None:
+            last.clear()
         nr, color, depth, radii, gb, bb, ib = _fwd(C, d)
         # train.py:244 L1 loss and its gradient sign(color - gt) / N for loss.backward()'s dloss = 1: value and
         # gradient in one pass (gs4d_l1_loss_grad, csrc/train_tail.hip; bitwise the two-pass form)
         loss, grad = TC.l1_loss_grad(color, gt, 1.0)
-        _bwd(C, d, radii, grad, gb, nr, bb, ib)
+        grads = _bwd(C, d, radii, grad, gb, nr, bb, ib)
         if dist:
             import torch.distributed as tdist
             tdist.all_reduce(loss)                    # the harness's loss all-reduce over RCCL
+        if last is not None:
+            last.update(color=color, depth=depth, radii=radii, loss=loss, grads=grads)
         return nr
     return step
+
+
+DUMP_BYTES = 64 * 1000 * 1000   # --dump-outputs writes at most this much in all
+# rasterize_gaussians_backward's tuple; the colour and 3D-covariance gradients are intermediates of a step that
+# passes SH coefficients, scales and rotations, and are not written out
+GRAD_NAMES = ("dL_dmeans2D", None, "dL_dopacity", "dL_dmeans3D", None, "dL_dsh", "dL_dscales", "dL_drotations")
+
+
+def dump_outputs(path, last):
+    """DIR/<name>.npy, float32, of what the last timed step returned.  When the arrays exceed DUMP_BYTES, each is
+    cut to its share: a sorted sample of its flattened elements, drawn without replacement by a generator of
+    fixed seed (the same elements in every run of the same configuration)."""
+    arrays = {k: last[k] for k in ("color", "depth", "radii", "loss")}
+    arrays.update({n: g for n, g in zip(GRAD_NAMES, last["grads"]) if n})
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    arrays["loss"] = arrays["loss"].reshape(-1)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES - 4096 * len(arrays)   # the .npy headers
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > budget:
+            keep = max(1, int(a.size * budget / total))
+            idx = np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def timed_steps(step, steps, warmup, dist, sync=True):

@@ -13,7 +13,7 @@ fi
 for rep in 1 2; do
 for v in cur $VARIANTS; do
   if [ $v = cur ]; then LP=""; else LP="4dgaussians-fast-train_amd/build/variant_$v"; fi
-  LD_LIBRARY_PATH=$LP${LD_LIBRARY_PATH:+:$LD_LIBRARY_PATH} timeout -k 10 200 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-train-step > $OUT/b_${v}_$rep.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/b_${v}_$rep.log; exit 1; }
+  LD_LIBRARY_PATH=$LP${LD_LIBRARY_PATH:+:$LD_LIBRARY_PATH} timeout -k 10 200 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-train-step > $OUT/b_${v}_$rep.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/b_${v}_$rep.log; exit 1; }
   python - $OUT/b_${v}_$rep.log $v <<'PY'
 import json,sys
 j=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -5,7 +5,7 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_${TAG:-r03a}
 mkdir -p $OUT
-ARGS="--steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extras"
+ARGS="--full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extras"
 timeout -k 10 60 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || echo "list rc=$?"
 run() {  # name, rocprofv3 args...; bench args from $BARGS
     local name=$1; shift

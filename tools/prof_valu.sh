@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_${TAG:-valu}
 mkdir -p $OUT
-ARGS="--steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extras"
+ARGS="--full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extras"
 run() {
     local name=$1; shift
     timeout -k 10 240 rocprofv3 "$@" -d $OUT/$name -o run --output-format csv -- python3 bench.py $ARGS > $OUT/bench_$name.log 2>&1 \

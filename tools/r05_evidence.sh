@@ -7,7 +7,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 400 --timeout
 rc=$?; tail -3 $OUT/gpu_tests.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || { echo "smoke rc=$?"; tail -5 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/bench.log; exit 1; }
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 python3 -c "
 import json; j=json.load(open('$OUT/bench.json'))

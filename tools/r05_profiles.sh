@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 T=${TAG:-r05b}
 TAG=$T bash tools/prof_valu.sh || exit $?
 OUT=gpurun_out/prof_$T
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/trace_tl -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extras --scene train_like > $OUT/bench_trace_tl.log 2>&1 || { echo "trace_tl rc=$?"; exit 1; }
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/trace_tl -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extras --scene train_like > $OUT/bench_trace_tl.log 2>&1 || { echo "trace_tl rc=$?"; exit 1; }
 TAG=$T bash tools/train_seq.sh | tail -1 || exit 1
 PROBE_ARGS="metric --bf16" TAG=${T}_bf16 bash tools/train_seq.sh | tail -1
 echo profiles done

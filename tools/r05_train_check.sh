@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_train_gpu.py tests/test_trainin
 rc=$?; grep -E "passed|failed|Error" $OUT/tests.log | tail -8; [ $rc -ne 0 ] && exit $rc
 TAG=${TAG}_f32 bash tools/train_seq.sh | tail -1 || exit 1
 PROBE_ARGS="metric --bf16" TAG=${TAG}_bf16 bash tools/train_seq.sh | tail -1 || exit 1
-timeout -k 10 400 python3 bench.py --no-cpu-baseline > $OUT/bench.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline > $OUT/bench.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/bench.log; exit 1; }
 grep '^{' $OUT/bench.log | tail -1 | python3 -c "
 import json,sys; j=json.loads(sys.stdin.read()); t=j.get('train_step',{})
 print('value', j['value'], 'ms', j['ms_per_step'], 'train', t.get('ms'), 'bf16', (t.get('bf16_mlp') or {}).get('ms'))

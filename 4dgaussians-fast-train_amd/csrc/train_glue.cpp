@@ -109,7 +109,7 @@ void densify_stats(const torch::Tensor &vs_grad, const torch::Tensor &visible, c
     // an empty visibility mask: radii > 0 filters (train.py's definition of the mask; radii required then)
     need(visible.numel() == 0 || (visible.scalar_type() == torch::kBool && visible.numel() == P && visible.is_cuda()),
          "visibility must be bool (P) or empty");
-    need(visible.numel() || radii.numel(), "densify_stats: an empty visibility mask needs the radii");
+    need(P == 0 || visible.numel() || radii.numel(), "densify_stats: an empty visibility mask needs the radii");
     need(grad_accum.numel() == P && denom.numel() == P, "accumulators must have P elements");
     c10::hip::HIPGuard guard(vs_grad.device().index());
     torch::Tensor vis = visible.contiguous();

@@ -381,10 +381,13 @@ __global__ __launch_bounds__(kTailThreads) void deform_tail_bwd_kernel(
         const float n0 = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
         const float nrm = fmaxf(n0, 1e-12f);
         const float xg = q[0] * g[0] + q[1] * g[1] + q[2] * g[2] + q[3] * g[3];
-        const float gn = n0 > 1e-12f ? -xg / (nrm * nrm) : 0.f;
+        // at or below eps (n0 may be 0: a zero quaternion, or squares that underflow) the gradient is g / eps alone,
+        // with no division by n0
+        const bool above = n0 > 1e-12f;
+        const float gn = above ? -xg / (nrm * nrm) : 0.f;
 #pragma unroll
         for (int c = 0; c < 4; c++) {
-            const float v = g[c] / nrm + gn * (q[c] / n0);
+            const float v = above ? g[c] / nrm + gn * (q[c] / n0) : g[c] / nrm;
             d_r[4 * (size_t)i + c] = v;
             if (g_dr) g_dr[4 * (size_t)i + c] = v;
         }

@@ -289,8 +289,13 @@ class GaussianModel:
         self._grow(self._clone_rows(grads, grad_threshold, scene_extent), empty)
 
     def densify_and_split(self, grads, grad_threshold, scene_extent, N=2):
-        """gaussian_model.py:415-441 (a no-op when nothing is selected, as there)"""
-        ids = self._split_rows(grads[:self._xyz.shape[0]], grad_threshold, scene_extent)
+        """gaussian_model.py:415-441 (a no-op when nothing is selected, as there).  grads may be shorter than the
+        model (rows cloned since it was formed): padded with zeros (:416-419), so those rows never split."""
+        P = self._xyz.shape[0]
+        g = grads.reshape(-1)[:P]
+        padded = torch.zeros(P, dtype=g.dtype, device=g.device)
+        padded[:g.shape[0]] = g
+        ids = self._split_rows(padded, grad_threshold, scene_extent)
         if ids.numel():
             self._grow(ids[:0], ids, N)
 

@@ -195,12 +195,13 @@ class _DeformTail(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, s, r, o, f_dc, f_rest, dx, ds, dr, d_o, dshs):
         c = lambda t: None if t is None else t.contiguous()
-        dshs_flat = None if dshs is None else dshs.reshape(dshs.shape[0], -1)
+        K = f_rest.shape[1] + 1  # explicit widths: -1 is ambiguous for a model without rows
+        dshs_flat = None if dshs is None else dshs.reshape(dshs.shape[0], 3 * K)
         means, scales, rot, opac, shs = _C.deform_tail_forward(xyz.contiguous(), s.contiguous(), r.contiguous(),
                                                                o.contiguous(), f_dc.contiguous(), f_rest.contiguous(),
                                                                c(dx), c(ds), c(dr), c(d_o), c(dshs_flat))
         ctx.save_for_backward(scales, r, dr, opac)
-        ctx.K = f_rest.shape[1] + 1
+        ctx.K = K
         ctx.has = tuple(t is not None for t in (dx, ds, dr, d_o, dshs))
         ctx.dshs_shape = None if dshs is None else dshs.shape
         ctx.set_materialize_grads(False)
@@ -210,7 +211,7 @@ class _DeformTail(torch.autograd.Function):
     def backward(ctx, g_means, g_scales, g_rot, g_opac, g_shs):
         scales, r, dr, opac = ctx.saved_tensors
         c = lambda t: None if t is None else t.contiguous()
-        g_shs_flat = None if g_shs is None else g_shs.contiguous().reshape(g_shs.shape[0], -1)
+        g_shs_flat = None if g_shs is None else g_shs.contiguous().reshape(g_shs.shape[0], 3 * ctx.K)
         has = ctx.has
         d_xyz, d_s, d_r, d_o, d_fdc, d_frest, g_dx, g_ds, g_dr, g_do = _C.deform_tail_backward(
             scales, r.contiguous(), c(dr), opac, c(g_means), c(g_scales), c(g_rot), c(g_opac), g_shs_flat, ctx.K,

@@ -42,7 +42,9 @@ int gs4d_l1_loss_backward(int64_t n, const int8_t *sign, const float *dloss, flo
  * NULL: zero), writes d xyz, d s, d r, d o, d f_dc and d f_rest (the slices of d shs, whose flat
  * (P, 3K) form is also the gradient of dshs), and the same values again into the deltas' gradients
  * g_dx, g_ds, g_dr, g_do where those are not NULL (separate buffers: autograd hands them to other
- * functions while the bases' gradients may become leaf .grad tensors). */
+ * functions while the bases' gradients may become leaf .grad tensors).  d r is F.normalize's gradient,
+ * g / max(n, eps) - [n > eps] q (q . g) / n^3 with q = r + dr, n = |q|, eps = 1e-12: g / eps at or below eps, finite
+ * for a zero quaternion. */
 int gs4d_deform_tail_forward(int P, int K, const float *xyz, const float *s, const float *r, const float *o,
                              const float *f_dc, const float *f_rest, const float *dx, const float *ds, const float *dr,
                              const float *d_o, const float *dshs, float *means, float *scales, float *rot,

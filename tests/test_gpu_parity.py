@@ -420,3 +420,64 @@ def test_flip_bands_cover_measured_operands(C, oracle, dev, cfg):
           flush=True)
     assert d_alpha <= PAR.FLIP_BAND_ALPHA / 2
     assert d_test_T <= PAR.FLIP_BAND_T / 2
+
+
+def _cov3d_of(s):
+    q = s["rotations"].astype(np.float64)
+    r, x, y, z = q.T
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                  2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                  2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
+    Cm = np.einsum("pij,pj,pkj->pik", R, s["scales"].astype(np.float64) ** 2, R)
+    return np.stack([Cm[:, 0, 0], Cm[:, 0, 1], Cm[:, 0, 2], Cm[:, 1, 1], Cm[:, 1, 2], Cm[:, 2, 2]], 1).astype(np.float32)
+
+
+@pytest.mark.parametrize("mode", ["colors+scales_rotations", "shs+cov3D"])
+def test_autograd_api_gradient_routing(C, dev, mode):
+    """_RasterizeGaussians.backward returns eight gradients by position; test_autograd_api passes SH, scales and
+    rotations only.  With colors_precomp + scales / rotations, and with shs + cov3D_precomp, each leaf's .grad is
+    bitwise the tensor _C.rasterize_gaussians_backward returns for that quantity on the same inputs (the path the
+    oracle tests hold), the leaves that are not passed get none, and a backward from the depth image alone leaves
+    every .grad None (no gradient flows from depth, as in the reference)."""
+    import diff_gaussian_rasterization as dgr
+    s = make_scene(500, 96, 64)
+    d = to_dev(s, dev)
+    settings = dgr.GaussianRasterizationSettings(
+        image_height=s["H"], image_width=s["W"], tanfovx=s["tanfovx"], tanfovy=s["tanfovy"], bg=d["bg"],
+        scale_modifier=float(s["scale_modifier"]), viewmatrix=d["viewmatrix"], projmatrix=d["projmatrix"],
+        sh_degree=int(s["sh_degree"]), campos=d["campos"], prefiltered=False, debug=False)
+    raster = dgr.GaussianRasterizer(settings)
+    colors = torch.tensor(np.random.default_rng(9).uniform(0, 1, (500, 3)).astype(np.float32), device=dev)
+    cov3D = torch.tensor(_cov3d_of(s), device=dev)
+    use_colors = mode.startswith("colors")
+    col_t, cov_t = (colors, None) if use_colors else (None, cov3D)
+
+    def leaves():
+        t = {k: d[k].clone().requires_grad_(True) for k in ("means3D", "shs", "opacities", "scales", "rotations")}
+        t["means2D"] = torch.zeros_like(t["means3D"], requires_grad=True)
+        t["colors_precomp"] = colors.clone().requires_grad_(True)
+        t["cov3D_precomp"] = cov3D.clone().requires_grad_(True)
+        return t
+    passed = ["means3D", "means2D", "opacities"] + (["colors_precomp", "scales", "rotations"] if use_colors
+                                                    else ["shs", "cov3D_precomp"])
+    t = leaves()
+    img, radii, depth = raster(**{k: t[k] for k in passed})
+    g, _ = make_upstream_grad(img.detach().cpu().numpy())
+    gt = torch.tensor(g, device=dev)
+    (img * gt).sum().backward()
+    fwd = c_forward(C, s, d, colors=col_t, cov3D=cov_t, use_sh=not use_colors)
+    assert torch.equal(fwd[1], img.detach()) and torch.equal(fwd[2], depth.detach()) and torch.equal(fwd[3], radii)
+    # (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
+    raw = dict(zip(("means2D", "colors_precomp", "opacities", "means3D", "cov3D_precomp", "shs", "scales", "rotations"),
+                   c_backward(C, s, d, fwd, gt, colors=col_t, cov3D=cov_t, use_sh=not use_colors)))
+    for k, leaf in t.items():
+        if k in passed:
+            assert leaf.grad is not None and leaf.grad.shape == leaf.shape, k
+            assert torch.equal(leaf.grad, raw[k]), k
+            assert k == "means2D" or bool(leaf.grad.any()), k
+        else:
+            assert leaf.grad is None, k
+    t = leaves()
+    img, radii, depth = raster(**{k: t[k] for k in passed})
+    depth.sum().backward()
+    assert all(leaf.grad is None for leaf in t.values())

@@ -8,6 +8,9 @@
 * the PLY layout of scene/gaussian_model.py:214-314 (header, attribute order, round trip);
 * the optimizer-state surgery of densify / prune / reset_opacity with torch.optim.Adam;
 * the learning-rate schedule of utils/general_utils.get_expon_lr_func.
+* densify_and_clone followed by densify_and_split with the same gradients against densify()'s single row plan;
+* the float64 restatements of the tail kernels' formulas (tests/train_edge_refs.py) against torch's own CPU fp32
+  graphs, inside the bars the GPU edge tests use.
 """
 import itertools
 import math
@@ -579,3 +582,109 @@ def test_splitk_chunk_rows_divides_p_or_falls_back():
         else:
             assert not any(P % d == 0 for d in range((3 * c0) // 4, 2 * c0 + 1) if d % 8 == 0), (P, c)
     assert _chunk_rows(100_000) == 2000
+
+
+def test_densify_clone_then_split_equals_densify():
+    """gaussian_model.py:501-506 calls densify_and_clone then densify_and_split with the SAME grads: after the
+    clone pass the model is longer than grads, which the split pass pads with zeros (:416-419), so the rows cloned
+    just before never split.  The two passes give, element for element, the rows, moments, statistics and table of
+    densify()'s single row plan under the same seed."""
+    a, b = _stepped_model(), _stepped_model()
+    grads = a.xyz_gradient_accum / a.denom
+    assert bool((torch.norm(grads, dim=-1) >= 5e-4).any())
+    torch.manual_seed(9)
+    a.densify(5e-4, 0.005, 1.0, None)
+    torch.manual_seed(9)
+    P0 = b._xyz.shape[0]
+    b.densify_and_clone(grads, 5e-4, 1.0)
+    assert b._xyz.shape[0] > P0 == grads.shape[0]
+    b.densify_and_split(grads, 5e-4, 1.0)
+    assert a._xyz.shape[0] == b._xyz.shape[0] > P0
+    ra, rb = _rows(a), _rows(b)
+    for n in ra:
+        for x, y in zip(ra[n][:3], rb[n][:3]):
+            assert torch.equal(x, y), n
+        assert float(ra[n][3]) == float(rb[n][3]), n
+    for name in ("xyz_gradient_accum", "denom", "max_radii2D", "_deformation_accum", "_deformation_table"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+
+
+def test_train_edge_refs_agree_with_torch_cpu(capsys):
+    """tests/train_edge_refs.py alone stays inside every bar it sets: on the planted inputs of
+    test_train_edges_gpu.py, torch's own CPU fp32 graphs (F.normalize / exp / sigmoid with autograd, the torch
+    formulation of the densification statistics, torch.optim.Adam, l1_loss_torch with autograd) agree with the
+    fp64 helpers within c * 2^-24 * magnitude, before any GPU is involved.  No bar was widened: the largest
+    fraction of a bar that torch's graphs use is printed per section."""
+    import torch.nn.functional as F
+    import train_edge_refs as R
+    from gs4d_train.losses import l1_loss_torch
+    used = {}
+
+    def hold(section, got, ref, what):
+        w = R.worst(got, ref)
+        used[section] = max(used.get(section, 0.0), w)
+        assert w <= 1.0, (section, what, w)
+
+    # deformation tail
+    for P, K, heads in ((257, 16, "all"), (257, 9, "mixed"), (257, 4, "none"), (1, 1, "all")):
+        base, deltas, ups = R.deform_inputs(P, K, heads)
+        leaves = [t.requires_grad_(True) for t in base] + [t.requires_grad_(True) for t in deltas if t is not None]
+        add = lambda a, b: a if b is None else a + b
+        sh = torch.cat((base[4], base[5]), dim=1)
+        outs = (add(base[0], deltas[0]), torch.exp(add(base[1], deltas[1])), F.normalize(add(base[2], deltas[2])),
+                torch.sigmoid(add(base[3], deltas[3])), sh if deltas[4] is None else sh + deltas[4].reshape(P, K, 3))
+        grads = torch.autograd.grad(sum((o * u).sum() for o, u in zip(outs, ups)), leaves)
+        ro, rg = R.deform_tail_ref(base, deltas, ups)
+        for o, k in zip(outs, ("means", "scales", "rot", "opac", "shs")):
+            hold("deform_tail", o, ro[k], (P, K, heads, k))
+        for g, k in zip(grads[:6], ("d_xyz", "d_s", "d_r", "d_o", "d_fdc", "d_frest")):
+            assert bool(torch.isfinite(g).all()), k
+            hold("deform_tail", g, rg[k], (P, K, heads, k))
+    # densification statistics (GaussianModel.add_densification_stats' torch formulation)
+    for P in (1, 257):
+        vs4, vis, radii, acc, den, mr = R.densify_inputs(P)
+        for v, r in ((vis, radii), (None, radii), (vis, None)):
+            ref, rden, rmr, mask = R.densify_stats_ref(vs4[:, :3], v, r, acc, den, mr)
+            a2, d2, m2 = acc.clone(), den.clone(), mr.clone()
+            if r is not None:
+                m2[mask] = torch.max(m2[mask], r[mask].float())
+            a2[mask] += torch.norm(vs4[mask, :2], dim=-1, keepdim=True)
+            d2[mask] += 1
+            hold("densify_stats", a2, ref, (P, v is None, r is None))
+            assert torch.equal(d2.double(), rden) and torch.equal(m2.double(), rmr)
+    # Adam: three steps, each against the helper started from the tensors before that step
+    params = [torch.nn.Parameter(p) for p in R.adam_case(97)]
+    groups = [{"params": params[:60], "betas": R.ADAM_HYPER[0][0], "eps": R.ADAM_HYPER[0][1]},
+              {"params": params[60:], "betas": R.ADAM_HYPER[1][0], "eps": R.ADAM_HYPER[1][1]}]
+    opt = torch.optim.Adam(groups, lr=R.ADAM_LR)
+    for step in range(3):
+        grads = R.adam_grads(params, step)
+        before = [(p.detach().clone(), opt.state[p]["exp_avg"].clone() if opt.state[p] else torch.zeros_like(p),
+                   opt.state[p]["exp_avg_sq"].clone() if opt.state[p] else torch.zeros_like(p),
+                   float(opt.state[p]["step"]) if opt.state[p] else 0.0) for p in params]
+        for p, g in zip(params, grads):
+            p.grad = g
+        opt.step()
+        for i, (p, g, (p0, m0, v0, t0)) in enumerate(zip(params, grads, before)):
+            if g is None:
+                continue
+            (b1, b2), eps = R.ADAM_HYPER[0 if i < 60 else 1]
+            rm, rv, rp = R.adam_ref(p0, g, m0, v0, b1, b2, eps, *R.adam_scalars(R.ADAM_LR, b1, b2, t0 + 1))
+            hold("adam", opt.state[p]["exp_avg"], rm, (step, i, "exp_avg"))
+            hold("adam", opt.state[p]["exp_avg_sq"], rv, (step, i, "exp_avg_sq"))
+            hold("adam", p, rp, (step, i, "param"))
+    # L1
+    for n in R.L1_SIZES:
+        x, y = R.l1_inputs(n)
+        x.requires_grad_(True)
+        loss = l1_loss_torch(x, y)
+        loss.backward(torch.tensor(0.37))
+        ref, grad = R.l1_ref(x, y, 0.37)
+        hold("l1", loss, ref, n)
+        # the signs exactly; torch's CPU MeanBackward divides by n (one rounding) where its GPU kernel and the
+        # header multiply by fl32(1 / n) (two): the header's form is within those 2 roundings of torch's here
+        assert torch.equal(torch.sign(x.grad), torch.sign(grad)), n
+        hold("l1", x.grad, R.Ref(grad.double(), grad.double().abs(), 2, 0.0), n)
+    with capsys.disabled():
+        print("\ntrain_edge_refs vs torch CPU fp32, largest error / bar:",
+              ", ".join(f"{k} {v:.3f}" for k, v in used.items()))

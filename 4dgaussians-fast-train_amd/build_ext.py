@@ -20,21 +20,25 @@ OUT = os.path.join(HERE, "diff_gaussian_rasterization")
 OBJ = os.path.join(HERE, "build", "obj")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ARCH = os.environ.get("GS4D_ARCH", "gfx950")
-HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backward.hip", "knn.hip", "train_tail.hip", "hexplane.hip", "capi.hip"]
+# the train step's kernels by subsystem: train_tail.hip (losses, Adam, statistics, the small streams) and the
+# deformation MLP's mlp_*.hip, all compiled alike
+TRAIN_SOURCES = ["train_tail.hip", "mlp_feature.hip", "mlp_heads_forward.hip", "mlp_heads_backward.hip", "mlp_gemm.hip"]
+HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backward.hip", "knn.hip", *TRAIN_SOURCES, "hexplane.hip", "capi.hip"]
 # Per-Gaussian math (K1, K8/K9) is compiled without FMA contraction: it costs nothing measurable
 # (those kernels are tiny) and keeps radii / tile rects -- discrete decisions -- bit-identical to the
 # oracle.  The per-pixel blend kernels keep contraction for throughput.
 # (package, pybind glue) pairs: each package gets an in-tree `_C` module over libgs4d
 BINDINGS = [("diff_gaussian_rasterization", "torch_glue.cpp"), ("simple_knn", "knn_glue.cpp"), ("gs4d_train", "train_glue.cpp")]
-NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "binning.hip", "knn.hip", "train_tail.hip", "hexplane.hip"}
+NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "binning.hip", "knn.hip", *TRAIN_SOURCES, "hexplane.hip"}
 # The blend kernels pack pixel pairs explicitly (ext_vector_type(2) -> v_pk_*_f32); the SLP vectorizer
 # would also pack their scalar horizontal adds, paying register moves for a v_pk_add_f32 (4 issue cycles)
 # where two v_add_f32 cost about 5 (tools/bench/valu_rates.hip), so it is off for render.hip.
 NO_SLP = {"render.hip"}
 # The blend kernels and the binning take LLVM's iterative ILP scheduler: measured on one box, render forward
 # 104.5 -> 103.3 us, backward 162.9 -> 161.2 us, the train-like tile sort 43.4 -> 42.5 us (tools/ab_lib.sh,
-# tools/ab_train_kernels.sh); the HexPlane backward got slower with it (+4 us) and train_tail.hip crashes the
-# register allocator under it, so the other files keep the default.
+# tools/ab_train_kernels.sh); the HexPlane backward got slower with it (+4 us) and the kernels of
+# train_tail.hip and mlp_*.hip crashed the register allocator under it (seen while they were one file; not
+# tried again file by file), so the other files keep the default.
 SCHED_ILP = {"render.hip", "binning.hip"}
 HIPCC_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-Wall",
                "-Wno-unused-result", "-I" + INCLUDE]
@@ -73,7 +77,7 @@ def build(force=False, verbose=False, report=True):
     was compiled or reused (mtimes of its sources, the headers and this script)."""
     os.makedirs(OBJ, exist_ok=True)
     done = []  # (artifact, "compiled" | "reused")
-    headers = [os.path.join(CSRC, h) for h in ("gs4d_math.h", "gs4d_internal.h", "radix_sort.h")] + [os.path.join(INCLUDE, h) for h in ("gs4d.h", "gs4d_train.h")]
+    headers = [os.path.join(CSRC, h) for h in ("gs4d_math.h", "gs4d_internal.h", "radix_sort.h", "train_internal.h")] + [os.path.join(INCLUDE, h) for h in ("gs4d.h", "gs4d_train.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def compile_one(src):

@@ -1,4 +1,5 @@
-"""Torch-facing wrappers of libgs4d's train-step kernels (include/gs4d_train.h, csrc/train_tail.hip).
+"""Torch-facing wrappers of libgs4d's train-step kernels (include/gs4d_train.h; csrc/train_tail.hip and,
+for the deformation MLP, csrc/mlp_*.hip).
 
 Importing this module loads the in-tree `gs4d_train._C` extension and fails loudly when it is not
 built: there is no silent torch fallback here.  (The reference's torch formulations live in the

@@ -54,8 +54,12 @@ int gs4d_deform_tail_backward(int P, int K, const float *scales, const float *r,
                               const float *g_shs, float *d_xyz, float *d_s, float *d_r, float *d_o, float *d_fdc,
                               float *d_frest, float *g_dx, float *g_ds, float *g_dr, float *g_do, void *stream);
 
-/* ---- split-K partial sums: out[i] = sum over s = 0 .. S-1 (in that order) of parts[s * n + i].  The
- * deformation MLP's weight gradients dW = dY^T X over P ~ 1e5 rows are split-K GEMMs
+/* ---- split-K partial sums: out[i] = sum over s = 0 .. S-1 of parts[s * n + i], in a fixed order that depends
+ * only on S, n and the pointers' alignment (the same bits on every run):
+ *   - S < 16, or n % 4 != 0, or parts / out not 16-byte aligned, or n > 2^26: slice order, s = 0, 1, .., S-1;
+ *   - else four quarters, quarter q = the slices [q S / 4, (q + 1) S / 4) (integer division) added in slice
+ *     order onto +0.0f, then out[i] = (q0 + q1) + (q2 + q3).
+ * The deformation MLP's weight gradients dW = dY^T X over P ~ 1e5 rows are split-K GEMMs
  * (gs4d_train/deformation.py _splitk_dw) whose per-chunk results this adds in one pass. */
 int gs4d_sum_slices(const float *parts, int S, int64_t n, float *out, void *stream);
 
@@ -267,7 +271,8 @@ int gs4d_heads_backward_bf16(const gs4d_heads_bwd_bf16 *args, void *scratch, voi
  * forward's w1t); bf16 MFMA, fp32 accumulation.  KW a multiple of 64, W in {64, 128}, 16-byte aligned. */
 int gs4d_mlp_dx_bf16(int P, int KW, int W, const uint16_t *da, const uint16_t *w1t, float *dh, void *stream);
 /* Its weight gradient dW1 (KW, W) fp32 = da^T hb over the P rows (da (P, KW), hb (P, W) bf16; W = 128, KW a multiple
- * of W): per 1024-row chunk and head a bf16-MFMA block (LDS transpose reads), the chunks summed in order. */
+ * of W): per 1024-row chunk and head a bf16-MFMA block (LDS transpose reads), the ceil(P / 1024) chunks summed by
+ * gs4d_sum_slices in its fixed order (above: a quarter tree from 16 chunks on). */
 size_t gs4d_mlp_dw_bf16_scratch_bytes(int P, int KW, int W);
 int gs4d_mlp_dw_bf16(int P, int KW, int W, const uint16_t *da, const uint16_t *hb, float *dw, void *scratch,
                      void *stream);
@@ -277,8 +282,10 @@ int gs4d_mlp_dw_bf16(int P, int KW, int W, const uint16_t *da, const uint16_t *h
  * {64, 128}; rows 16-byte aligned. */
 int gs4d_mlp_dx_f32(int P, int KW, int W, const float *da, const float *w1t, float *dh, void *stream);
 /* Its weight gradient dW1 (KW, W) = da^T h over the P rows (da (P, KW), h (P, W) row-major): per row chunk and
- * 64-row block of dW1 an f32-MFMA block, its waves summed in a fixed order, the chunks summed in order (scratch:
- * gs4d_mlp_dw_f32_scratch_bytes). */
+ * 64-row block of dW1 an f32-MFMA block, its waves summed in a fixed order, the chunks summed by gs4d_sum_slices in its fixed order
+ * (above; scratch: gs4d_mlp_dw_f32_scratch_bytes).  The chunk count follows the device's compute-unit count (one
+ * resident round of workgroups), so dW1's bits are the same on every run and process on one device model, but
+ * may differ in the last places between devices with different CU counts. */
 size_t gs4d_mlp_dw_f32_scratch_bytes(int P, int KW, int W);
 int gs4d_mlp_dw_f32(int P, int KW, int W, const float *da, const float *h, float *dw, void *scratch, void *stream);
 

@@ -576,6 +576,25 @@ def test_heads_backward_matches_fp64(P, W, ns):
         assert float((out[3 + 2 * i].double() - rb).abs().max() / sb) <= 1e-5
 
 
+def test_heads_backward_wide_head_needs_w_64_or_128():
+    """The 48-wide head has MFMA kernels for W in {64, 128} only: gs4d_heads_backward rejects it at W = 256
+    (the argument check that keeps a wide head from ever reaching a narrow kernel) and serves it at W = 128
+    with results of the documented shapes (da, db1, dW2, db2)."""
+    from gs4d_train import _C
+    torch.manual_seed(48)
+    P, n = 8, 48
+    for W, ok in ((256, False), (128, True)):
+        a = torch.relu(torch.randn(P, W, device="cuda"))
+        gs, w2 = [torch.randn(P, n, device="cuda")], [torch.randn(n, W, device="cuda")]
+        if not ok:
+            with pytest.raises(RuntimeError):
+                _C.heads_backward(a, gs, w2)
+            continue
+        out = _C.heads_backward(a, gs, w2)
+        assert [tuple(t.shape) for t in out] == [(P, W), (W,), (n, W), (n,)]
+        assert all(t.dtype == torch.float32 and bool(torch.isfinite(t).all()) for t in out)
+
+
 @pytest.mark.parametrize("P,N,K,col0", [(100_000, 640, 128, 0), (100_003, 640, 128, 0), (2048, 640, 128, 0),
                                          (5000, 192, 64, 0), (3001, 256, 256, 0), (7777, 128, 128, 5)])
 def test_mlp_gemms_match_fp64(P, N, K, col0):

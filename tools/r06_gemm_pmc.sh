@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over the fp32 heads-block GEMM kernels (one counter group per run); GS4D_MLP_SHAPE passes through
+# PMC passes over the fp32 heads-block GEMM kernels (one counter group per run)
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT

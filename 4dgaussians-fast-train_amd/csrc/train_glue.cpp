@@ -99,6 +99,75 @@ torch::Tensor l1_backward(const torch::Tensor &sign, const torch::Tensor &dloss_
     return grad;
 }
 
+namespace {
+// (B, C, H, W) of an image tensor (C, H, W) or (B, C, H, W)
+struct ImageDims {
+    int B, C, H, W;
+};
+ImageDims image_dims(const torch::Tensor &x, const torch::Tensor &y, const char *what) {
+    need(x.sizes() == y.sizes(), std::string(what) + ": shapes differ");
+    need(x.is_cuda() && y.is_cuda(), std::string(what) + ": inputs must be HIP (GPU) tensors");
+    need(x.dim() == 3 || x.dim() == 4, std::string(what) + ": images must be (C, H, W) or (B, C, H, W)");
+    const int o = x.dim() == 4 ? 1 : 0;
+    for (int i = 0; i < x.dim(); i++)
+        need(x.size(i) <= std::numeric_limits<int>::max(), std::string(what) + ": dimension too large");
+    return {o ? (int)x.size(0) : 1, (int)x.size(o), (int)x.size(o + 1), (int)x.size(o + 2)};
+}
+}  // namespace
+
+// ssim forward (gs4d_ssim_forward): returns (mean (0-dim), per-image means (B), maps for the backward or an
+// undefined tensor when want_maps is false: the values only, nothing else allocated)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ssim_forward(const torch::Tensor &x_, const torch::Tensor &y_,
+                                                                     bool want_maps) {
+    const ImageDims d = image_dims(x_, y_, "ssim");
+    c10::hip::HIPGuard guard(x_.device().index());
+    torch::Tensor x = x_.to(torch::kFloat32).contiguous(), y = y_.to(torch::kFloat32).contiguous();
+    torch::Tensor mean = torch::empty({}, x.options()), per_image = torch::empty({d.B}, x.options()), maps;
+    if (want_maps) maps = torch::empty({3, x.numel()}, x.options());
+    check(gs4d_ssim_forward(d.B, d.C, d.H, d.W, x.data_ptr<float>(), y.data_ptr<float>(),
+                            want_maps ? maps.data_ptr<float>() : nullptr, mean.data_ptr<float>(),
+                            per_image.data_ptr<float>(),
+                            ticket_scratch(x, gs4d_ssim_scratch_bytes(d.B, d.C, d.H, d.W), 2), stream_of(x)),
+          "ssim forward");
+    return {mean, per_image, maps};
+}
+
+// ssim backward (gs4d_ssim_backward): dvalue holds one upstream gradient (of the mean) or B (of the per-image means)
+torch::Tensor ssim_backward(const torch::Tensor &x_, const torch::Tensor &y_, const torch::Tensor &maps,
+                            const torch::Tensor &dvalue_) {
+    const ImageDims d = image_dims(x_, y_, "ssim");
+    gpu_f32(maps, "ssim maps");
+    need(maps.numel() == 3 * x_.numel(), "ssim backward: maps must hold 3 floats per element");
+    c10::hip::HIPGuard guard(x_.device().index());
+    torch::Tensor x = x_.to(torch::kFloat32).contiguous(), y = y_.to(torch::kFloat32).contiguous();
+    torch::Tensor dvalue = dvalue_.to(torch::kFloat32).contiguous();
+    need(dvalue.is_cuda(), "ssim backward: the upstream gradient must be a HIP (GPU) tensor");
+    need(dvalue.numel() == 1 || dvalue.numel() == d.B, "ssim backward: 1 or B upstream gradients");
+    const int per_image = dvalue_.dim() > 0 && dvalue.numel() == d.B;
+    torch::Tensor grad = torch::empty(x.sizes(), x.options());
+    check(gs4d_ssim_backward(d.B, d.C, d.H, d.W, x.data_ptr<float>(), y.data_ptr<float>(), maps.data_ptr<float>(),
+                             dvalue.data_ptr<float>(), per_image, grad.data_ptr<float>(), stream_of(x)),
+          "ssim backward");
+    return grad;
+}
+
+// the train step's L1 + D-SSIM image loss (gs4d_l1_dssim_loss_grad): returns (L1, ssim, d/dx of
+// dloss * (L1 + lambda * (1 - ssim)))
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> l1_dssim_loss_grad(const torch::Tensor &x_, const torch::Tensor &y_,
+                                                                           double lambda, double dloss) {
+    const ImageDims d = image_dims(x_, y_, "l1_dssim_loss_grad");
+    c10::hip::HIPGuard guard(x_.device().index());
+    torch::Tensor x = x_.to(torch::kFloat32).contiguous(), y = y_.to(torch::kFloat32).contiguous();
+    torch::Tensor l1 = torch::empty({}, x.options()), ssim = torch::empty({}, x.options());
+    torch::Tensor grad = torch::empty(x.sizes(), x.options()), maps = torch::empty({3, x.numel()}, x.options());
+    check(gs4d_l1_dssim_loss_grad(d.B, d.C, d.H, d.W, x.data_ptr<float>(), y.data_ptr<float>(), (float)lambda,
+                                  (float)dloss, maps.data_ptr<float>(), l1.data_ptr<float>(), ssim.data_ptr<float>(),
+                                  grad.data_ptr<float>(),
+                                  ticket_scratch(x, gs4d_ssim_scratch_bytes(d.B, d.C, d.H, d.W), 2), stream_of(x)),
+          "l1_dssim_loss_grad");
+    return {l1, ssim, grad};
+}
+
 void densify_stats(const torch::Tensor &vs_grad, const torch::Tensor &visible, const torch::Tensor &radii,
                    torch::Tensor &grad_accum, torch::Tensor &denom, torch::Tensor &max_radii) {
     gpu_f32(vs_grad, "viewspace grad");
@@ -1131,6 +1200,9 @@ PYBIND11_MODULE(_C, m) {
     m.def("l1_forward", &l1_forward);
     m.def("l1_backward", &l1_backward);
     m.def("l1_loss_grad", &l1_loss_grad);
+    m.def("ssim_forward", &ssim_forward);
+    m.def("ssim_backward", &ssim_backward);
+    m.def("l1_dssim_loss_grad", &l1_dssim_loss_grad);
     m.def("densify_stats", &densify_stats);
     m.def("adam_step", &adam_step);
     m.def("version", []() { return std::string(gs4d_version()); });

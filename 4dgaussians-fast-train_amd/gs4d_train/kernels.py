@@ -1,5 +1,5 @@
-"""Torch-facing wrappers of libgs4d's train-step kernels (include/gs4d_train.h; csrc/train_tail.hip and,
-for the deformation MLP, csrc/mlp_*.hip).
+"""Torch-facing wrappers of libgs4d's train-step kernels (include/gs4d_train.h; csrc/train_tail.hip,
+csrc/ssim.hip and, for the deformation MLP, csrc/mlp_*.hip).
 
 Importing this module loads the in-tree `gs4d_train._C` extension and fails loudly when it is not
 built: there is no silent torch fallback here.  (The reference's torch formulations live in the
@@ -12,7 +12,7 @@ import torch.optim.optimizer as _optim_mod
 
 from . import _C
 
-__all__ = ["deform_tail", "l1_loss", "densify_stats", "FusedAdam", "hexplane", "hexplane_points", "set_deterministic", "hexplane_regulation", "hexplane_regulation_value",
+__all__ = ["deform_tail", "l1_loss", "ssim", "l1_dssim_loss_and_grad", "densify_stats", "FusedAdam", "hexplane", "hexplane_points", "set_deterministic", "hexplane_regulation", "hexplane_regulation_value",
            "hexplane_regulation_accumulate_grad"]
 
 
@@ -46,6 +46,44 @@ def l1_loss_and_grad(network_output, gt, dloss=1.0):
         return _C.l1_loss_grad(x, y, float(dloss))
     loss, sign = _C.l1_forward(x, y)
     return loss, _C.l1_backward(sign, torch.full((1,), float(dloss), device=x.device)).to(x.dtype)
+
+
+class _Ssim(torch.autograd.Function):
+    """utils/loss_utils.py:36-66 in two launches (csrc/ssim.hip): forward returns the mean or the per-image
+    means and keeps the map's derivatives for the backward; only img1 receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, size_average):
+        mean, per_image, maps = _C.ssim_forward(x, y, True)
+        ctx.save_for_backward(x, y, maps)
+        return mean if size_average else per_image
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y, maps = ctx.saved_tensors
+        return _C.ssim_backward(x, y, maps, grad_out), None, None
+
+
+def ssim(img1, img2, window_size=11, size_average=True):
+    """Drop-in for utils/loss_utils.ssim on (C, H, W) or (B, C, H, W) images: the mean of the SSIM map, or the
+    per-image means with size_average=False (batched input).  img2 receives no gradient (as in training); without
+    a gradient to form (torch.no_grad, evaluation) only the value is computed."""
+    if window_size != 11:
+        raise ValueError(f"ssim: the kernel is built for window_size=11, got {window_size}")
+    if not size_average and img1.dim() != 4:
+        raise ValueError("ssim: size_average=False needs batched (B, C, H, W) images")
+    if not (torch.is_grad_enabled() and img1.requires_grad):
+        mean, per_image, _ = _C.ssim_forward(img1.detach(), img2.detach(), False)
+        return mean if size_average else per_image
+    return _Ssim.apply(img1.to(torch.float32), img2.detach(), bool(size_average)).to(img1.dtype)
+
+
+def l1_dssim_loss_and_grad(image, gt, lambda_dssim, dloss=1.0):
+    """(L1, ssim, image_grad) of the train step's image loss dloss * (L1 + lambda_dssim * (1 - ssim(image, gt)))
+    (train.py:244, :255-257) in two launches (gs4d_l1_dssim_loss_grad): the detached values and the complete
+    gradient w.r.t. image for an upstream gradient `dloss` known on the host, no autograd node."""
+    Ll1, ssim_value, grad = _C.l1_dssim_loss_grad(image.detach(), gt.detach(), float(lambda_dssim), float(dloss))
+    return Ll1, ssim_value, grad.to(image.dtype)
 
 
 @torch.no_grad()

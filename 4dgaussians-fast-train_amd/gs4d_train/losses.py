@@ -3,7 +3,8 @@
 These are the reference's formulations: train.py:244 takes the L1 loss of the batch and, when
 `lambda_dssim != 0`, adds `lambda_dssim * (1 - ssim(image, gt))` (train.py:255-257).  The fused L1
 kernel the train step uses by default is gs4d_train.kernels.l1_loss; `l1_loss_torch` is its parity
-reference and the `fused=False` path.
+reference and the `fused=False` path.  Likewise `ssim` here is the parity reference and the
+`fused=False` path of gs4d_train.kernels.ssim / l1_dssim_loss_and_grad (csrc/ssim.hip).
 """
 from math import exp
 

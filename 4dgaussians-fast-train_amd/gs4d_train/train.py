@@ -54,7 +54,7 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
                                                                                        device=dev)
         visibility_filter = torch.cat(vis_list).any(dim=0) if vis_list else torch.zeros(P, dtype=torch.bool,
                                                                                       device=dev)
-    image_grad = None  # fused path, no D-SSIM: the L1's image gradient, formed with its value in one pass
+    image_grad = None  # fused path: the image loss's gradient, formed with its value (L1: one pass; + D-SSIM: two)
     if images:
         image_tensor = images[0] if one else torch.cat(images, 0)
         gt_image_tensor = gts[0] if one else torch.cat(gts, 0)
@@ -68,9 +68,13 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
             Ll1, image_grad = l1_loss_and_grad(image_tensor, gt_image_tensor[:, :3, :, :], share)
             loss = Ll1 * share if data_parallel else Ll1
         elif fused:
-            from .kernels import l1_loss
-            Ll1 = l1_loss(image_tensor, gt_image_tensor[:, :3, :, :])
-            loss = Ll1 * share if data_parallel else Ll1
+            # the same with D-SSIM: loss = (L1 + lambda * (1 - ssim)) * share, both values and the complete image
+            # gradient in two launches (gs4d_l1_dssim_loss_grad)
+            from .kernels import l1_dssim_loss_and_grad
+            Ll1, ssim_value, image_grad = l1_dssim_loss_and_grad(image_tensor, gt_image_tensor[:, :3, :, :],
+                                                                 opt.lambda_dssim, share)
+            loss = Ll1 + opt.lambda_dssim * (1.0 - ssim_value)
+            loss = loss * share if data_parallel else loss
         else:
             Ll1 = l1_loss_torch(image_tensor, gt_image_tensor[:, :3, :, :])
             loss = Ll1 * share if data_parallel else Ll1
@@ -87,7 +91,7 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
         else:
             reg = gaussians.compute_regulation(*reg_w)
             loss = loss + reg * reg_scale
-    if opt.lambda_dssim != 0 and images:
+    if opt.lambda_dssim != 0 and images and not fused:
         from .losses import ssim
         loss = loss + opt.lambda_dssim * (1.0 - ssim(image_tensor, gt_image_tensor)) * (
             len(mine) / len(views) if data_parallel else 1.0)

@@ -32,6 +32,33 @@ int gs4d_l1_loss_grad(int64_t n, const float *x, const float *y, float dloss, fl
                       void *stream);
 int gs4d_l1_loss_backward(int64_t n, const int8_t *sign, const float *dloss, float *grad, void *stream);
 
+/* ---- SSIM / D-SSIM: utils/loss_utils.py:36-66 ssim(img1, img2, window_size=11, size_average): the 11x11
+ * Gaussian window (sigma 1.5, normalised), zero padding of 5, one filter per channel, C1 = 0.01^2,
+ * C2 = 0.03^2, map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), applied separably
+ * (11 taps along the rows, then 11 along the columns) in one launch per direction.  x, y (B, C, H, W).
+ * Status 1 for a null pointer or a negative dimension; a zero dimension is an empty batch: status 0, no
+ * launch, the values zeroed.  H * W < 2^31, B <= 65535.
+ * scratch: gs4d_ssim_scratch_bytes(B, C, H, W) bytes, all zero on entry and left zero, kept by the caller as
+ * the L1 loss's above (the totals are fp64 partials per 32x32 tile summed in a fixed order per image, then
+ * over the images in order: bitwise repeatable). */
+size_t gs4d_ssim_scratch_bytes(int B, int C, int H, int W);
+/* *mean = map.mean() (size_average=True), per_image[b] = map[b].mean() (size_average=False).  maps: NULL for
+ * the values only, else 3 * B*C*H*W floats that receive what gs4d_ssim_backward needs (the map's derivatives
+ * by the three filtered moments of x that it depends on). */
+int gs4d_ssim_forward(int B, int C, int H, int W, const float *x, const float *y, float *maps, float *mean,
+                      float *per_image, void *scratch, void *stream);
+/* grad_x = the gradient autograd derives for img1: dvalue (device) is the upstream gradient of the mean
+ * (per_image = 0: one float) or of the B per-image means (per_image = 1: B floats); each is divided by the
+ * element count it averages over.  A gather: no atomics, each element written once.  y gets no gradient. */
+int gs4d_ssim_backward(int B, int C, int H, int W, const float *x, const float *y, const float *maps,
+                       const float *dvalue, int per_image, float *grad_x, void *stream);
+/* The train step's image loss, train.py:244 + :255-257, value and gradient in two launches for an upstream
+ * gradient known on the host (as gs4d_l1_loss_grad): *l1 = mean |x - y|, *ssim = ssim(x, y) (the mean over
+ * everything), grad_x = d/dx of dloss * (l1 + lambda * (1 - ssim)).  maps: 3 * B*C*H*W floats of workspace
+ * (caller-provided); scratch as gs4d_ssim_forward's. */
+int gs4d_l1_dssim_loss_grad(int B, int C, int H, int W, const float *x, const float *y, float lambda, float dloss,
+                            float *maps, float *l1, float *ssim, float *grad_x, void *scratch, void *stream);
+
 /* ---- the deformation's tail and the activations before the rasterizer, in one pass each way:
  * scene/deformation.py:140-146 (residual adds of the heads' outputs, features = cat(f_dc, f_rest),
  * scene/gaussian_model.py:116-118) and gaussian_renderer/__init__.py:97-99 (exp, normalize, sigmoid):

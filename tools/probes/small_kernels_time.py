@@ -1,6 +1,8 @@
 """Device time of the train step's smaller HIP passes at its shapes (diagnostic, GPU): the first deformation
-layer's backward (P = 100k, 32 -> 128), the deformation tail both ways, HIP events over R calls.  For A/B of
-libgs4d variants (LD_LIBRARY_PATH=4dgaussians-fast-train_amd/build/variant_<name>)."""
+layer's backward (P = 100k, 32 -> 128), the deformation tail both ways, HIP events over R calls, and the image
+losses (L1; SSIM and the fused L1 + D-SSIM beside torch's losses.ssim) with the spread over 9 rounds of R calls.
+For A/B of libgs4d variants (LD_LIBRARY_PATH=4dgaussians-fast-train_amd/build/variant_<name>).
+Usage: small_kernels_time.py [--ssim-only]"""
 import os
 import sys
 
@@ -48,8 +50,27 @@ def main():
     # the L1 value + gradient at the bench image (3 x 1014 x 1352)
     img, gt = torch.rand(3, 1014, 1352, device="cuda"), torch.rand(3, 1014, 1352, device="cuda")
     rows.append(("l1_loss_grad", lambda: _C.l1_loss_grad(img, gt, 1.0)))
-    for name, fn in rows:
+    for name, fn in ([] if "--ssim-only" in sys.argv else rows):
         print(f"{name:28s} {timed(fn):8.1f} us", flush=True)
+    # SSIM forward + backward and the fused L1 + D-SSIM (two launches each) beside losses.ssim forward + backward
+    # (torch: grouped conv2d + element-wise + autograd) on the same tensors: median [min, max] of 9 rounds
+    from gs4d_train.kernels import l1_dssim_loss_and_grad, ssim
+    from gs4d_train.losses import ssim as ssim_torch
+
+    def fwd_bwd(f, x, y):
+        xa = x.detach().requires_grad_(True)
+        f(xa, y).backward()
+
+    for shape in ((1, 3, 1014, 1352), (1, 3, 800, 800)):
+        x, y = torch.rand(shape, device="cuda"), torch.rand(shape, device="cuda")
+        n = x.numel()
+        for name, fn, nbytes in ((f"ssim fwd+bwd {shape[2]}x{shape[3]}", lambda: fwd_bwd(ssim, x, y), 44 * n),
+                                 (f"ssim value only {shape[2]}x{shape[3]}", lambda: ssim(x, y), 8 * n),
+                                 (f"l1_dssim_loss_grad {shape[2]}x{shape[3]}", lambda: l1_dssim_loss_and_grad(x, y, 0.2), 44 * n),
+                                 (f"losses.ssim fwd+bwd {shape[2]}x{shape[3]}", lambda: fwd_bwd(ssim_torch, x, y), None)):
+            ts = sorted(timed(fn) for _ in range(9))
+            rate = f"  {nbytes / ts[4] / 1e6:6.2f} TB/s of its {nbytes / 1e6:.0f} MB" if nbytes else ""
+            print(f"{name:32s} {ts[4]:8.1f} us [{ts[0]:.1f}, {ts[-1]:.1f}]{rate}", flush=True)
 
 
 if __name__ == "__main__":

@@ -73,6 +73,7 @@ size_t max_emit_chunks(int P, int T) {
 constexpr int kCountThreads = 1024;
 constexpr int kCountMaxT = 16384;  // LDS bins of one chunk (64 KiB)
 constexpr int kColWaves = 16, kColPer = 32;  // column scan: 16 waves x 32 chunks per lane
+constexpr int kOrderBins = 1024;             // run-length bins of the tile order (order_tiles)
 int count_items(int L, int T) {
     // GS4D_BINNING=radix: the radix-sort binning everywhere (A/B diagnostics; read once per process,
     // so a forward and its backward always agree on the buffer layout)
@@ -457,14 +458,24 @@ __device__ __forceinline__ int xcd_chunk(int b, int nblk) {
     const int q = nblk >> 3, r = nblk & 7, x = b & 7, j = b >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
+// Workgroup 0 of the launch orders the tiles for the blend kernels instead (order_tiles, below): that needs the
+// tile scan's ranges only, is serial work of one workgroup, and the chunks leave most of the chip idle.
+// Workgroups 1 .. nblk take the chunks; the dynamic LDS holds max(T, kOrderBins) words.
+__device__ void order_tiles(const uint2 *__restrict__ ranges, int T, uint32_t *__restrict__ order, uint32_t *s_bin);
 template <int ITEMS>
 __global__ __launch_bounds__(kCountThreads) void tile_scatter_kernel(const uint32_t *__restrict__ keys,
                                                                      const uint32_t *__restrict__ n_dev, int T,
                                                                      const uint32_t *__restrict__ offs,
-                                                                     uint32_t *__restrict__ upos) {
+                                                                     uint32_t *__restrict__ upos, int nblk,
+                                                                     const uint2 *__restrict__ ranges,
+                                                                     uint32_t *__restrict__ order) {
     extern __shared__ uint32_t s_off[];
+    if (blockIdx.x == 0) {
+        order_tiles(ranges, T, order, s_off);
+        return;
+    }
     const int n = count_of(0, n_dev), tid = threadIdx.x;
-    const int chunk = xcd_chunk((int)blockIdx.x, (int)gridDim.x);
+    const int chunk = xcd_chunk((int)blockIdx.x - 1, nblk);
     const size_t c0 = (size_t)chunk * (kCountThreads * ITEMS);
     if (c0 >= (size_t)n) return;
     uint32_t key[ITEMS];
@@ -492,8 +503,9 @@ static void launch_counting(const BinningState &b, int L, int T, ImageState img,
                        b.tile_hist);
     hipLaunchKernelGGL(tile_scan_kernel, dim3((T + 63) / 64), dim3(kCountThreads), 0, s, b.tile_hist, n_dev, T, C,
                        img.ranges, look, err);
-    hipLaunchKernelGGL(tile_scatter_kernel<ITEMS>, dim3(nblk), dim3(kCountThreads), lds, s, b.keys[0], n_dev, T,
-                       b.tile_hist, b.upos);
+    hipLaunchKernelGGL(tile_scatter_kernel<ITEMS>, dim3(nblk + 1), dim3(kCountThreads),
+                       4 * (size_t)std::max(T, kOrderBins), s, b.keys[0], n_dev, T, b.tile_hist, b.upos, nblk, img.ranges,
+                       img.order);
 }
 
 // ---- K4: per-tile sort by (depth bits, Gaussian id) -------------------------------------------------
@@ -633,7 +645,7 @@ __device__ void merge_sort_run(uint32_t *__restrict__ seg, int n, const uint32_t
 // start run at low occupancy, so a long tile started late ends the kernel late.  tile_order_kernel
 // (one workgroup) orders the tiles longest run first (a counting sort on min(run, 1023), the order
 // inside a length arbitrary: it only schedules, every tile's result is its own).
-constexpr int kOrderBins = 1024, kOrderBatch = 8;
+constexpr int kOrderBatch = 8;
 __device__ void order_tiles(const uint2 *__restrict__ ranges, int T, uint32_t *__restrict__ order, uint32_t *s_bin) {
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int i = tid; i < kOrderBins; i += nt) s_bin[i] = 0;
@@ -704,13 +716,15 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint2 *__restric
 
 // Tiles with more than kWaveSortMax instances (shorter runs are sorted in registers by the render
 // forward): one workgroup each (workgroup t + 1 for tile t).  Up to 2048: wave sorts + merge path
-// (merge_sort_run); longer: runs of kSortCap in LDS merged by the bitonic network's global steps.  Workgroup 0
-// orders the tiles (order_tiles), so one launch does both (a launch costs ~4 us of the timeline).
+// (merge_sort_run); longer: runs of kSortCap in LDS merged by the bitonic network's global steps.  After the radix
+// binning (do_order) workgroup 0 orders the tiles (order_tiles), so one launch does both (a launch costs ~4 us of
+// the timeline); after the counting binning the scatter launch has ordered them already.
 __global__ __launch_bounds__(256) void tile_sort_kernel(const uint2 *__restrict__ ranges, int T,
                                                         uint32_t *__restrict__ order,
                                                         const uint32_t *__restrict__ gid_by_e,
                                                         const float *__restrict__ depths, uint32_t *__restrict__ upos,
-                                                        uint32_t *__restrict__ tkey_hi, uint32_t *__restrict__ tkey_lo) {
+                                                        uint32_t *__restrict__ tkey_hi, uint32_t *__restrict__ tkey_lo,
+                                                        int do_order) {
     // 32 KiB of LDS, five workgroups per CU: the merge path's two 2048-key buffers, or a long tile's
     // 2048-key run (TileSortLds, 24 KiB).  (A 48 KiB layout for 4096-key LDS runs held three per CU; this
     // kernel is latency-bound per workgroup -- dependent key gathers, binary searches, barriers -- so the
@@ -718,7 +732,7 @@ __global__ __launch_bounds__(256) void tile_sort_kernel(const uint2 *__restrict_
     __shared__ uint64_t s_mem[2 * kSortCap];
     TileSortLds &s = *reinterpret_cast<TileSortLds *>(s_mem);
     if (blockIdx.x == 0) {
-        order_tiles(ranges, T, order, reinterpret_cast<uint32_t *>(s_mem));
+        if (do_order) order_tiles(ranges, T, order, reinterpret_cast<uint32_t *>(s_mem));
         return;
     }
     const uint2 r = ranges[blockIdx.x - 1];
@@ -817,7 +831,7 @@ hipError_t launch_binning(const Args &a, GeomState g, const int *radii, BinningS
                            img.ranges);
     }
     hipLaunchKernelGGL(tile_sort_kernel, dim3(T + 1), dim3(256), 0, s, img.ranges, T, img.order, b.gid_by_e, g.depths,
-                       b.upos, b.tmp_hi, b.tmp_lo);
+                       b.upos, b.tmp_hi, b.tmp_lo, b.count_items ? 0 : 1);
     return hipGetLastError();
 }
 

@@ -21,8 +21,9 @@ OBJ = os.path.join(HERE, "build", "obj")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ARCH = os.environ.get("GS4D_ARCH", "gfx950")
 # the train step's kernels by subsystem: train_tail.hip (losses, Adam, statistics, the small streams), ssim.hip
-# (the D-SSIM loss) and the deformation MLP's mlp_*.hip, all compiled alike
-TRAIN_SOURCES = ["train_tail.hip", "ssim.hip", "mlp_feature.hip", "mlp_heads_forward.hip", "mlp_heads_backward.hip", "mlp_gemm.hip"]
+# (the D-SSIM loss), the deformation MLP's mlp_*.hip and deform_infer.hip (the MLP at inference), all compiled alike
+TRAIN_SOURCES = ["train_tail.hip", "ssim.hip", "mlp_feature.hip", "mlp_heads_forward.hip", "mlp_heads_backward.hip", "mlp_gemm.hip",
+                 "deform_infer.hip"]
 HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backward.hip", "knn.hip", *TRAIN_SOURCES, "hexplane.hip", "capi.hip"]
 # Per-Gaussian math (K1, K8/K9) is compiled without FMA contraction: it costs nothing measurable
 # (those kernels are tiny) and keeps radii / tile rects -- discrete decisions -- bit-identical to the

@@ -27,6 +27,8 @@ static int fail(int code, const std::string &msg) {
     g_last_error = msg;
     return code;
 }
+// the same for the train-step translation units (train_internal.h)
+int train_fail(int code, const std::string &msg) { return fail(code, msg); }
 
 #define GS4D_HIP(expr)                                                                                                  \
     do {                                                                                                               \

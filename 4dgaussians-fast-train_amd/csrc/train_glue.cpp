@@ -299,6 +299,85 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> hexplane_forward(const t
     return {feat, packed, order};
 }
 
+// The field over planes already packed channels-last (hexplane_forward's second result) in a given point order
+// (its third): inference samples one model at many times, where the planes and the canonical means -- hence the
+// pack and the order -- are constants.  widths / heights: the 6 * levels planes' W and H, F their features.  order
+// must be a permutation of 0 .. N-1, as hexplane_forward returns it (its values are not checked here).
+torch::Tensor hexplane_forward_packed(const torch::Tensor &pts, const torch::Tensor &packed, int64_t F,
+                                      std::vector<int64_t> widths, std::vector<int64_t> heights,
+                                      const torch::Tensor &order) {
+    gpu_f32(pts, "hexplane pts");
+    gpu_f32(packed, "hexplane packed planes");
+    need(pts.dim() == 2 && pts.size(1) == 4, "hexplane: pts must be (N, 4)");
+    need(!widths.empty() && widths.size() % 6 == 0 && widths.size() == heights.size() &&
+             widths.size() <= 6 * GS4D_HEXPLANE_MAX_LEVELS,
+         "hexplane: 6 plane sizes per level");
+    const int N = (int)pts.size(0);
+    need(order.is_cuda() && order.scalar_type() == torch::kInt32 && order.is_contiguous() && order.numel() == N &&
+             order.device() == pts.device() && packed.device() == pts.device(),
+         "hexplane: order must be a contiguous int32 GPU tensor of N indices on pts' device");
+    std::vector<int> W(widths.begin(), widths.end()), H(heights.begin(), heights.end());
+    gs4d_hexplane_layout lay;
+    check(gs4d_hexplane_layout_init(&lay, (int)(widths.size() / 6), (int)F, W.data(), H.data()), "hexplane layout");
+    need(packed.numel() == lay.total, "hexplane: packed buffer size");
+    c10::hip::HIPGuard guard(pts.device().index());
+    torch::Tensor feat = torch::empty({N, (int64_t)lay.levels * lay.F}, pts.options());
+    check(gs4d_hexplane_forward(N, pts.data_ptr<float>(), (const uint32_t *)order.data_ptr<int>(), &lay,
+                                packed.data_ptr<float>(), feat.data_ptr<float>(), (void *)stream_of(pts)),
+          "hexplane forward");
+    return feat;
+}
+
+// ---- the deformation network at inference (gs4d_deform_infer): feat (P, F) -> (means, scales, rot, opac, shs).
+// w1 (kW, W) / b1 (kW): the active heads' first layers stacked in head order; roles[i]: GS4D_ROLE_* of head i.
+std::vector<torch::Tensor> deform_infer(const torch::Tensor &feat, const torch::Tensor &wf, const torch::Tensor &bf,
+                                        const torch::Tensor &w1, const torch::Tensor &b1,
+                                        const std::vector<torch::Tensor> &w2s, const std::vector<torch::Tensor> &b2s,
+                                        const std::vector<int64_t> &roles, const torch::Tensor &xyz,
+                                        const torch::Tensor &s, const torch::Tensor &r, const torch::Tensor &o,
+                                        const torch::Tensor &f_dc, const torch::Tensor &f_rest, bool activate) {
+    const int k = (int)w2s.size();
+    need(k >= 1 && k <= 5 && (int)b2s.size() == k && (int)roles.size() == k, "deform_infer: 1-5 heads");
+    for (const torch::Tensor *t : std::initializer_list<const torch::Tensor *>{&feat, &wf, &bf, &w1, &b1, &xyz, &s, &r, &o,
+                                                                              &f_dc, &f_rest})
+        gpu_f32(*t, "deform_infer operand");
+    const int64_t P = feat.size(0);
+    need(feat.dim() == 2 && wf.dim() == 2 && w1.dim() == 2 && wf.size(1) == feat.size(1) && w1.size(1) == wf.size(0) &&
+             w1.size(0) == k * wf.size(0) && bf.numel() == wf.size(0) && b1.numel() == w1.size(0),
+         "deform_infer: feat (P, F), Wf (W, F), bf (W), W1 (kW, W), b1 (kW)");
+    need(f_rest.dim() == 3 && f_rest.size(2) == 3, "deform_infer: f_rest (P, K-1, 3)");
+    const int64_t K = 1 + f_rest.size(1);
+    for (const torch::Tensor *t : std::initializer_list<const torch::Tensor *>{&xyz, &s, &r, &o, &f_dc, &f_rest})
+        need(t->dim() >= 1 && t->size(0) == P && t->device() == feat.device(), "deform_infer: bases with P rows on feat's device");
+    need(xyz.numel() == 3 * P && s.numel() == 3 * P && r.numel() == 4 * P && o.numel() == P && f_dc.numel() == 3 * P &&
+             f_rest.numel() == 3 * (K - 1) * P,
+         "deform_infer: xyz / scales (P, 3), rotations (P, 4), opacity (P, 1), f_dc (P, 1, 3), f_rest (P, K-1, 3)");
+    c10::hip::HIPGuard guard(feat.device().index());
+    gs4d_deform_infer_args a{};
+    a.P = (int)P, a.F = (int)feat.size(1), a.W = (int)wf.size(0), a.K = (int)K, a.k = k, a.activate = activate ? 1 : 0;
+    a.feat = feat.data_ptr<float>(), a.wf = wf.data_ptr<float>(), a.bf = bf.data_ptr<float>();
+    a.w1 = w1.data_ptr<float>(), a.b1 = b1.data_ptr<float>();
+    for (int i = 0; i < k; i++) {
+        gpu_f32(w2s[i], "deform_infer W2");
+        gpu_f32(b2s[i], "deform_infer b2");
+        need(w2s[i].dim() == 2 && w2s[i].size(1) == a.W && b2s[i].numel() == w2s[i].size(0),
+             "deform_infer: W2_i (n_i, W), b2_i (n_i)");
+        a.role[i] = (int)roles[i], a.n[i] = (int)w2s[i].size(0);
+        a.w2[i] = w2s[i].data_ptr<float>(), a.b2[i] = b2s[i].data_ptr<float>();
+    }
+    auto means = torch::empty({P, 3}, feat.options()), scales = torch::empty({P, 3}, feat.options()),
+         rot = torch::empty({P, 4}, feat.options()), opac = torch::empty({P, 1}, feat.options()),
+         shs = torch::empty({P, K, 3}, feat.options());
+    a.xyz = xyz.data_ptr<float>(), a.s = s.data_ptr<float>(), a.r = r.data_ptr<float>(), a.o = o.data_ptr<float>();
+    a.f_dc = f_dc.data_ptr<float>(), a.f_rest = K > 1 ? f_rest.data_ptr<float>() : nullptr;
+    a.means = means.data_ptr<float>(), a.scales = scales.data_ptr<float>(), a.rot = rot.data_ptr<float>();
+    a.opac = opac.data_ptr<float>(), a.shs = shs.data_ptr<float>();
+    const int st = gs4d_deform_infer(&a, (void *)stream_of(feat));
+    if (st != 0)
+        throw std::runtime_error("deform_infer failed (status " + std::to_string(st) + "): " + gs4d_last_error());
+    return {means, scales, rot, opac, shs};
+}
+
 // returns (dpts (N, 4), plane gradients (1, F, H, W) each)
 std::tuple<torch::Tensor, std::vector<torch::Tensor>> hexplane_backward(const torch::Tensor &pts_,
                                                                          std::vector<torch::Tensor> planes,
@@ -1195,6 +1274,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("deform_tail_forward", &deform_tail_forward);
     m.def("deform_tail_backward", &deform_tail_backward);
     m.def("hexplane_forward", &hexplane_forward, py::arg("pts"), py::arg("planes"), py::arg("order") = py::none());
+    m.def("hexplane_forward_packed", &hexplane_forward_packed, py::arg("pts"), py::arg("packed"), py::arg("F"),
+          py::arg("widths"), py::arg("heights"), py::arg("order"));
+    m.def("deform_infer", &deform_infer, py::arg("feat"), py::arg("wf"), py::arg("bf"), py::arg("w1"), py::arg("b1"),
+          py::arg("w2"), py::arg("b2"), py::arg("roles"), py::arg("xyz"), py::arg("s"), py::arg("r"), py::arg("o"),
+          py::arg("f_dc"), py::arg("f_rest"), py::arg("activate") = true);
     m.def("hexplane_backward", &hexplane_backward, py::arg("pts"), py::arg("planes"), py::arg("packed"),
           py::arg("dfeat"), py::arg("order"), py::arg("deterministic") = true);
     m.def("l1_forward", &l1_forward);

@@ -1,12 +1,17 @@
 // train_internal.h -- the few things two or more of the train-step translation units share (train_tail.hip,
-// ssim.hip, mlp_feature.hip, mlp_heads_forward.hip, mlp_heads_backward.hip, mlp_gemm.hip): the MFMA fragment
+// ssim.hip, mlp_feature.hip, mlp_heads_forward.hip, mlp_heads_backward.hip, mlp_gemm.hip, deform_infer.hip): the MFMA fragment
 // types and LDS tile addressing of the bf16 weight-gradient kernels, the CU count, and the last-workgroup totals
 // of the loss kernels (train_tail.hip's L1 and regularisers, ssim.hip).  Whatever one file alone uses stays in
 // that file.
 #pragma once
+#include <string>
+
 #include "gs4d_internal.h"
 
 namespace gs4d {
+
+// sets gs4d_last_error()'s text for the calling thread and returns `code` (capi.hip)
+int train_fail(int code, const std::string &msg);
 
 constexpr int kHbMaxHeads = 8;  // heads of one deformation block (argument structs of the forward and the backward)
 

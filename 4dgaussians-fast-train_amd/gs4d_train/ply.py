@@ -9,6 +9,8 @@
 * `deformation.pth`, `deformation_table.pth`, `deformation_accum.pth` -- torch.save of the
   deformation network's state dict and the two per-Gaussian tensors (gaussian_model.py:233-249);
   loaded with weights_only=True (tensors only, nothing executed from the file).
+* `save_frame` -- one timestamp of a dynamic model as a static `point_cloud.ply`, the per-frame file of
+  export_perframe_3DGS.py:55-73,100-106 (the values of gs4d_train.infer.get_state_at_time).
 * scene/__init__.py:143-150 lays them out as <model>/point_cloud/iteration_<i>/{point_cloud.ply, *.pth}.
 
 The PLY codec is self-contained (the reference uses the `plyfile` package, absent here); it writes
@@ -92,6 +94,23 @@ def save_gaussians(path, g):
     opac = g._opacity.detach().cpu().numpy()
     scale = g._scaling.detach().cpu().numpy()
     rot = g._rotation.detach().cpu().numpy()
+    names = attribute_names(f_dc.shape[1], f_rest.shape[1], scale.shape[1], rot.shape[1])
+    attrs = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opac, scale, rot), axis=1)
+    write_ply(path, {k: attrs[:, i] for i, k in enumerate(names)})
+
+
+def save_frame(path, state, camera_or_time):
+    """One frame of a dynamic model as a static 3DGS point cloud: the file export_perframe_3DGS.py:55-73,100-106
+    writes per test camera.  state: gs4d_train.infer.prepare's capture; camera_or_time: a camera (its .time) or a
+    time.  The columns are save_gaussians' with the values of infer.get_state_at_time -- the deformed raw means,
+    scales, rotations and SHs, the UNDEFORMED opacity (the reference's quirk) -- and zero normals."""
+    from .infer import state_at_time
+    t = camera_or_time.time if hasattr(camera_or_time, "time") else camera_or_time
+    xyz, scale, rot, _, shs = (v.detach() for v in state_at_time(state, t, activate=False))
+    n_dc = state.f_dc.shape[1]
+    flat = lambda v: v.transpose(1, 2).flatten(start_dim=1).contiguous().cpu().numpy()
+    f_dc, f_rest = flat(shs[:, :n_dc]), flat(shs[:, n_dc:])
+    xyz, scale, rot, opac = (v.cpu().numpy() for v in (xyz, scale, rot, state.opacity))
     names = attribute_names(f_dc.shape[1], f_rest.shape[1], scale.shape[1], rot.shape[1])
     attrs = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opac, scale, rot), axis=1)
     write_ply(path, {k: attrs[:, i] for i, k in enumerate(names)})

@@ -389,6 +389,39 @@ typedef struct gs4d_heads_block_fwd_bf16 {
 } gs4d_heads_block_fwd_bf16;
 int gs4d_heads_block_forward_bf16(const gs4d_heads_block_fwd_bf16 *args, void *stream);
 
+/* ---- The deformation network at inference, one launch from the field features to the rasterizer's inputs
+ * (scene/deformation.py:51-55,73-78,97-146 and gaussian_renderer/__init__.py:94-99): feature_out with
+ * defor_depth <= 1, the heads, forward_dynamic's residual adds, and render()'s activations.
+ *   h = relu(feat Wf^T + bf);  for each head i: a_i = relu(h W1_i^T + b1_i), d_i = a_i W2_i^T + b2_i (P, n_i);
+ *   means = xyz + d_pos, scales = s + d_scales, rot = r + d_rot, opac = o + d_opacity,
+ *   shs = cat(f_dc, f_rest) + d_shs.reshape(P, 16, 3)
+ * and with activate != 0 the activations of gs4d_deform_tail_forward above, with its eps and its shs layout of K
+ * coefficients: scales = exp(.), rot = . / max(|.|, 1e-12), opac = sigmoid(.).  A role without a head passes its
+ * base through (activated when activate is set); all five outputs are always written in full.  Nothing else is
+ * written: no h, no a, no deltas.  f32 MFMA, exact f32 products, each point's sums in one fixed order (the same
+ * bits whatever the point's row).
+ * (F, W) in {(32, 128), (64, 64), (32, 64)}; 1 <= k <= 5 heads, each role at most once, n_i = 3, 3, 4, 1, 48 for
+ * role pos, scales, rot, opacity, shs; an shs head needs K = 16.  Anything else is status 1 with a
+ * gs4d_last_error() text, before any HIP call; P = 0 is a successful no-op; with no head at all the caller uses
+ * gs4d_deform_tail_forward.  feat (P, F), wf (W, F), bf (W), w1 (kW, W) = the heads' first-layer weights stacked
+ * in head order, b1 (kW), w2[i] (n_i, W), b2[i] (n_i); bases and outputs as gs4d_deform_tail_forward's.  feat, wf,
+ * w1, w2[i], rot and shs 16-byte aligned.  GS4D_TRAIN_ERR_LDS when the device cannot give the kernel its LDS
+ * (4 ((W + npad) (W + 8) + W (F + 8) + 2 W + npad) bytes, npad = the widest head's n rounded up to 16: 117,440
+ * at (32, 128) with shs). */
+enum { GS4D_ROLE_POS = 0, GS4D_ROLE_SCALES = 1, GS4D_ROLE_ROT = 2, GS4D_ROLE_OPACITY = 3, GS4D_ROLE_SHS = 4 };
+typedef struct gs4d_deform_infer_args {
+    int P, F, W, K; /* points, field features, hidden width, SH coefficients */
+    int k;          /* active heads */
+    int activate;
+    const float *feat, *wf, *bf, *w1, *b1;
+    int role[5], n[5];
+    const float *w2[5];
+    const float *b2[5];
+    const float *xyz, *s, *r, *o, *f_dc, *f_rest;
+    float *means, *scales, *rot, *opac, *shs;
+} gs4d_deform_infer_args;
+int gs4d_deform_infer(const gs4d_deform_infer_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

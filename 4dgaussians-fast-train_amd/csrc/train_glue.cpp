@@ -1246,7 +1246,49 @@ torch::Tensor sum_slices(torch::Tensor parts) {
     return out;
 }
 
+namespace {
+char *voxel_scratch_cb(void *ctx, size_t n) {
+    auto *t = static_cast<torch::Tensor *>(ctx);
+    t->resize_({(int64_t)n});
+    return reinterpret_cast<char *>(t->data_ptr());
+}
+}  // namespace
+
+// gs4d_voxel_downsample: (points (N, 3), colors (N, 3) or None, voxel_size) -> (points (M, 3), colors (M, 3) or None,
+// counts (M) int32), rows ascending in the voxels' linear index.  Synchronises the current stream (twice).
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>, torch::Tensor> voxel_downsample(
+    const torch::Tensor &points_, const c10::optional<torch::Tensor> &colors_, double voxel_size) {
+    need(points_.is_cuda(), "voxel_downsample: points must be a HIP (GPU) tensor; there is no CPU path");
+    need(points_.dim() == 2 && points_.size(1) == 3, "voxel_downsample: points must have dimensions (num_points, 3)");
+    need(points_.size(0) < ((int64_t)1 << 30), "voxel_downsample: at most 2^30 - 1 points");
+    const bool has_colors = colors_.has_value() && colors_->defined();
+    if (has_colors) {
+        need(colors_->is_cuda(), "voxel_downsample: colors must be a HIP (GPU) tensor; there is no CPU path");
+        need(colors_->device() == points_.device(), "voxel_downsample: points and colors must be on one device");
+        need(colors_->sizes() == points_.sizes(), "voxel_downsample: colors must have the points' shape");
+    }
+    c10::hip::HIPGuard guard(points_.device().index());
+    const int N = (int)points_.size(0);
+    torch::Tensor pts = points_.to(torch::kFloat32).contiguous(), cols;
+    if (has_colors) cols = colors_->to(torch::kFloat32).contiguous();
+    torch::Tensor out_p = torch::empty({N, 3}, pts.options()), out_c;
+    if (has_colors) out_c = torch::empty({N, 3}, pts.options());
+    torch::Tensor counts = torch::empty({N}, pts.options().dtype(torch::kInt32));
+    torch::Tensor scratch = torch::empty({0}, pts.options().dtype(torch::kUInt8));
+    int M = 0;
+    const int st = gs4d_voxel_downsample(N, pts.data_ptr<float>(), has_colors ? cols.data_ptr<float>() : nullptr, voxel_size,
+                                         out_p.data_ptr<float>(), has_colors ? out_c.data_ptr<float>() : nullptr,
+                                         counts.data_ptr<int32_t>(), &M, voxel_scratch_cb, &scratch, stream_of(pts));
+    if (st != GS4D_OK)
+        throw std::runtime_error(std::string(gs4d_last_error()) + " (status " + std::to_string(st) + ")");
+    // the M rows in storage of their own: the N-row buffers go back to the allocator
+    c10::optional<torch::Tensor> colors_out;
+    if (has_colors) colors_out = out_c.narrow(0, 0, M).clone();
+    return {out_p.narrow(0, 0, M).clone(), colors_out, counts.narrow(0, 0, M).clone()};
+}
+
 PYBIND11_MODULE(_C, m) {
+    m.def("voxel_downsample", &voxel_downsample, py::arg("points"), py::arg("colors"), py::arg("voxel_size"));
     m.def("hexplane_points", &hexplane_points);
     m.def("hexplane_points_backward", &hexplane_points_backward, py::arg("dpts"), py::arg("aabb"),
           py::arg("add") = py::none());

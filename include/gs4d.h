@@ -111,6 +111,30 @@ int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int wi
 int gs4d_knn_mean_dist(int P, const float *points, float *mean_dists, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
                        void *stream);
 
+/* Instant4D grid pruning: replaces the Open3D voxel_down_sample call of utils/grid_pruning.py:16-41, which
+ * scene/__init__.py:106-119 runs on the initial cloud in front of create_from_pcd (and so in front of
+ * gs4d_knn_mean_dist).  Semantics (Open3D's PointCloud::VoxelDownSample, with a defined row order):
+ *   - origin = per-axis minimum of the points (as fp64) - voxel_size / 2;
+ *   - voxel index per axis = floor((double(p) - origin) / voxel_size): fp64, a true division, no contraction,
+ *     so it equals numpy's for the same inputs;
+ *   - one output row per occupied voxel: the arithmetic mean of that voxel's points (and colours), summed in
+ *     fp64 in a fixed order and rounded once to fp32; out_counts[row] = how many points fell in;
+ *   - rows ascend in the linear index (iz * ny + iy) * nx + ix, n* = largest index + 1 (Open3D's order is its
+ *     hash map's, i.e. unspecified);
+ *   - normals are not produced (create_from_pcd ignores them).
+ * points / colors: N x 3 fp32 device arrays; colors may be NULL, and out_colors is NULL exactly when it is.
+ * out_points / out_colors (N x 3) and out_counts (N int32, may be NULL) have room for N rows; the first
+ * *num_voxels = M rows are written.  Results are bitwise repeatable (no floating-point atomics).
+ * The call synchronises `stream` twice -- once to read the six bounds, once to read M -- as gs4d_forward does
+ * once for num_rendered; the scratch buffer may be released when it returns.
+ * GS4D_ERR_ARG (gs4d_last_error() begins "voxel_downsample:"), before any launch: N < 0 or N >= 2^30,
+ * voxel_size not finite or <= 0, a NULL required pointer or allocator, colors / out_colors not both set or
+ * both NULL; after the bounds readback: a NaN or infinite coordinate, an axis of 2^21 voxels or more.
+ * N == 0 is a successful no-op with M = 0. */
+int gs4d_voxel_downsample(int N, const float *points, const float *colors, double voxel_size, float *out_points,
+                          float *out_colors, int32_t *out_counts, int *num_voxels, gs4d_alloc_fn scratch_alloc,
+                          void *scratch_ctx, void *stream);
+
 /* Diagnostic for the parity tests (no reference counterpart): for n (Gaussian, pixel) pairs, o G (the
  * blend's alpha before the 0.99 cap) and the base-2 exponent log2(G), evaluated by the exact arithmetic
  * of the blend kernels from the packed splat records a gs4d_forward left in geometry_buffer (P Gaussians,

@@ -323,18 +323,24 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
     return GS4D_OK;
 }
 
-int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int width, int height,
-                     const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
-                     float scale_modifier, const float *rotations, const float *cov3D_precomp,
-                     const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
-                     float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
-                     const float *dL_dpix, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity,
-                     float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
-                     float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream_,
-                     int view_transposed) {
+}  // extern "C"
+
+// gs4d_backward_ex (DEPTH = false) and gs4d_backward_depth (DEPTH = true): the same orchestration over the
+// colour-only or the depth-gradient instantiations of the three backward stages.
+template <bool DEPTH>
+static int backward_impl(int P, int D, int M, int R, const float *background, int width, int height,
+                         const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                         float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                         const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                         float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                         const float *dL_dpix, const float *dL_ddepth, float *dL_dmean2D, float *dL_dconic,
+                         float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
+                         float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug,
+                         void *stream_, int view_transposed) {
     hipStream_t stream = (hipStream_t)stream_;
     if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "backward: bad sizes");
     if (P == 0) return GS4D_OK;
+    if (DEPTH && (!dL_ddepth || !dL_dpix)) return fail(GS4D_ERR_ARG, "backward_depth: missing dL_ddepth or dL_dpix");
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !means3D)
         return fail(GS4D_ERR_ARG, "backward: missing buffers");
     if (shs && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
@@ -365,20 +371,67 @@ int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int wi
     if (R > 0) {
         b = BinningState::carve(binning_buffer, R, T);
         const float *color_ptr = colors_precomp;  // NULL -> the forward's rgb (rasterizer_impl.cu:392)
-        GS4D_REPEATED_STAGE("render_backward",
-                            launch_render_backward(a, g, b.gid_by_e, b.upos, img, color_ptr, dL_dpix, contrib, stream));
+        if (DEPTH)
+            GS4D_REPEATED_STAGE("render_backward", launch_render_backward_depth(a, g, b.gid_by_e, b.upos, img, dL_dpix,
+                                                                                dL_ddepth, contrib, stream));
+        else
+            GS4D_REPEATED_STAGE("render_backward", launch_render_backward(a, g, b.gid_by_e, b.upos, img, color_ptr,
+                                                                          dL_dpix, contrib, stream));
     }
-    GS4D_STAGE("contrib_reduce", launch_contrib_reduce(a, g, b, R, contrib, reduce_scratch, dL_dmean2D, dconic,
-                                                       dL_dopacity, dL_dcolor, stream));
     const float *cov3D_ptr = cov3D_precomp ? cov3D_precomp : g.cov3D;  // rasterizer_impl.cu:414
-    GS4D_STAGE("gaussian_backward",
-               launch_gaussian_backward(a, g, R, reduce_scratch, radii_ptr, means3D, shs, scales, rotations, cov3D_ptr,
-                                        dL_dmean2D, dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                        dL_dscale, dL_drot, stream));
+    if (DEPTH) {
+        GS4D_STAGE("contrib_reduce", launch_contrib_reduce_depth(a, g, b, R, contrib, reduce_scratch, dL_dmean2D, dconic,
+                                                                 dL_dopacity, dL_dcolor, stream));
+        GS4D_STAGE("gaussian_backward",
+                   launch_gaussian_backward_depth(a, g, R, reduce_scratch, radii_ptr, means3D, shs, scales, rotations,
+                                                  cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
+                                                  dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream));
+    } else {
+        GS4D_STAGE("contrib_reduce", launch_contrib_reduce(a, g, b, R, contrib, reduce_scratch, dL_dmean2D, dconic,
+                                                           dL_dopacity, dL_dcolor, stream));
+        GS4D_STAGE("gaussian_backward",
+                   launch_gaussian_backward(a, g, R, reduce_scratch, radii_ptr, means3D, shs, scales, rotations,
+                                            cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
+                                            dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream));
+    }
     if (dL_dconic && (float *)dconic != dL_dconic)
         GS4D_HIP(hipMemcpyAsync(dL_dconic, dconic, 16 * (size_t)P, hipMemcpyDeviceToDevice, stream));
     end_marks();
     return GS4D_OK;
+}
+
+extern "C" {
+
+int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int width, int height,
+                     const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                     float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                     const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                     float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                     const float *dL_dpix, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity,
+                     float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
+                     float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
+                     int view_transposed) {
+    return backward_impl<false>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                                tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, dL_dmean2D,
+                                dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+}
+
+int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int width, int height,
+                        const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                        float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                        const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                        float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                        const float *dL_dpix, const float *dL_ddepth, float *dL_dmean2D, float *dL_dconic,
+                        float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
+                        float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug,
+                        void *stream, int view_transposed) {
+    return backward_impl<true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                               tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dmean2D,
+                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                               scratch_alloc, scratch_ctx, debug, stream, view_transposed);
 }
 
 int gs4d_forward(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,

@@ -201,6 +201,20 @@ hipError_t launch_pair_alpha(GeomState g, int n, const int *gid, const int *px, 
                              hipStream_t s);
 hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos, ImageState img,
                                   const float *colors, const float *dL_dpix, float *contrib, hipStream_t s);
+// the depth-gradient backward (gs4d_backward_depth): the same three stages with dL/ddepth; the records' float 9
+// carries W3 = sum w dL/ddepth, whose per-Gaussian sum travels in dL_dconic's unused .z slot
+hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
+                                        ImageState img, const float *dL_dpix, const float *dL_ddepth, float *contrib,
+                                        hipStream_t s);
+hipError_t launch_contrib_reduce_depth(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+                                       char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
+                                       float *dL_dcolor, hipStream_t s);
+hipError_t launch_gaussian_backward_depth(const Args &a, GeomState g, int R, char *scratch, const int *radii,
+                                          const float *means3D, const float *shs, const float *scales,
+                                          const float *rotations, const float *cov3D, float *dL_dmean2D,
+                                          float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
+                                          hipStream_t s);
 size_t contrib_scratch_bytes(int R, int P);
 hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,

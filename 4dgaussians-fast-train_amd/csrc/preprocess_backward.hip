@@ -30,13 +30,16 @@ struct GradOut {
     const float4 *conic_opacity;
     float hw, hh;
 };
+// NV = 10 (the depth-gradient backward): R[9] = W3, the sum of w dL/ddepth, parked in the conic gradient's
+// unused .z slot until gaussian_grads turns it into dL/dmean3D and clears the slot.
+template <int NV>
 __device__ __forceinline__ void write_grads(const GradOut &o, uint32_t g, const float *R) {
     const float4 co = o.conic_opacity[g];
     const float op = co.w;
     o.mean2D[3 * g + 0] = o.hw * op * (-co.x * R[1] - co.y * R[2]);
     o.mean2D[3 * g + 1] = o.hh * op * (-co.z * R[2] - co.y * R[1]);
     o.mean2D[3 * g + 2] = 0.f;
-    o.conic[g] = make_float4(-0.5f * op * R[3], -0.5f * op * R[4], 0.f, -0.5f * op * R[5]);
+    o.conic[g] = make_float4(-0.5f * op * R[3], -0.5f * op * R[4], NV == 10 ? R[9] : 0.f, -0.5f * op * R[5]);
     o.opacity[g] = R[0];
     o.color[3 * g + 0] = R[6];
     o.color[3 * g + 1] = R[7];
@@ -52,32 +55,35 @@ __device__ __forceinline__ void write_zero_grads(const GradOut &o, uint32_t g) {
     o.color[3 * g + 1] = 0.f;
     o.color[3 * g + 2] = 0.f;
 }
+template <int NV>
 __device__ __forceinline__ void store9(float4 *p, const float *acc) {
     p[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
     p[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    p[2] = make_float4(acc[8], 0.f, 0.f, 0.f);
+    p[2] = make_float4(acc[8], NV == 10 ? acc[NV - 1] : 0.f, 0.f, 0.f);
 }
+template <int NV>
 __device__ __forceinline__ void add9(float *acc, const float4 *p) {
     const float4 a = p[0], b = p[1], c = p[2];
     acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
     acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
     acc[8] += c.x;
+    if (NV == 10) acc[NV - 1] += c.y;
 }
 
 // One step of the wave's segmented inclusive scan by DPP moves (no LDS): lane l takes the (sums, flag) of
 // the lane CTRL names (row_shr:n inside rows of 16, row_bcast:15 / :31 across rows, only the rows RM
 // enables; lanes without a source read zeros, the identity) and adds its sums unless a segment head
 // lies between them.
-template <int CTRL, int RM>
-__device__ __forceinline__ void seg_scan_step(float acc[9], bool &f) {
+template <int CTRL, int RM, int NV>
+__device__ __forceinline__ void seg_scan_step(float (&acc)[NV], bool &f) {
     const bool fu = __builtin_amdgcn_update_dpp(0, (int)f, CTRL, RM, 0xF, false) != 0;
-    float up[9];
+    float up[NV];
 #pragma unroll
-    for (int q = 0; q < 9; q++)
+    for (int q = 0; q < NV; q++)
         up[q] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[q]), CTRL, RM, 0xF, false));
     if (!f) {
 #pragma unroll
-        for (int q = 0; q < 9; q++) acc[q] += up[q];
+        for (int q = 0; q < NV; q++) acc[q] += up[q];
     }
     f = f || fu;
 }
@@ -86,7 +92,8 @@ __device__ __forceinline__ void seg_scan_step(float acc[9], bool &f) {
 // slots, so a segmented inclusive scan (fixed shuffle tree) sums each Gaussian's piece of the wave.
 // Pieces that are a whole Gaussian are written out; a piece continuing from the previous wave goes
 // to part[w][0], a piece that starts a Gaussian and continues into the next wave to part[w][1];
-// e_first[g] = the Gaussian's first slot.
+// e_first[g] = the Gaussian's first slot.  NV = 10 also sums the records' float 9 (W3), in the same order.
+template <int NV>
 __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *__restrict__ n_dev,
                                                                const uint32_t *__restrict__ gid_by_e,
                                                                const float4 *__restrict__ rec, GradOut o,
@@ -99,7 +106,7 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
     const int e = w * 64 + lane;
     const bool valid = e < n;
     const uint32_t key = valid ? gid_by_e[e] & kGidMask : 0xFFFFFFFFu;
-    float acc[9];
+    float acc[NV];
     {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
         if (valid) {
@@ -110,6 +117,7 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
         acc[0] = a.x; acc[1] = a.y; acc[2] = a.z; acc[3] = a.w;
         acc[4] = b.x; acc[5] = b.y; acc[6] = b.z; acc[7] = b.w;
         acc[8] = c.x;
+        if (NV == 10) acc[NV - 1] = c.y;
     }
     uint32_t kp = __shfl_up(key, 1), kn = __shfl_down(key, 1);
     if (lane == 0) kp = e > 0 ? gid_by_e[e - 1] & kGidMask : 0xFFFFFFFFu;
@@ -129,9 +137,9 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
     const bool head0 = __ballot(head) & 1ull;
     if (valid && (tail || lane == 63)) {
         const bool starts = lane != fe || head0;  // the piece starts at its Gaussian's first slot
-        if (starts && tail) write_grads(o, key, acc);
-        else if (!starts) store9(part + ((size_t)w * 2) * 3, acc);
-        else store9(part + ((size_t)w * 2 + 1) * 3, acc);
+        if (starts && tail) write_grads<NV>(o, key, acc);
+        else if (!starts) store9<NV>(part + ((size_t)w * 2) * 3, acc);
+        else store9<NV>(part + ((size_t)w * 2 + 1) * 3, acc);
     }
 }
 
@@ -140,6 +148,9 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
 // following wave up to the one holding its last slot -- and a Gaussian without instances gets zeros.
 // Then K8 + K9 without the SH part: dL/dcov3D, dL/dscale, dL/drot stored; dL/dmean3D's covariance +
 // projection terms returned (the caller adds the SH term, backward.cu:390, and stores it).
+// NV = 10: dL/dmean3D also takes W3 d(p_view.z)/dmean, the view matrix's depth row (forward.cu:250's
+// p_view.z = m[2] x + m[6] y + m[10] z + m[14]); culled Gaussians (radii 0) get nothing.
+template <int NV>
 __device__ __forceinline__ V3 gaussian_grads(
     int idx, const Args &a, const GeomState &g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
@@ -153,10 +164,10 @@ __device__ __forceinline__ V3 gaussian_grads(
         } else {
             const uint32_t e0 = e_first[idx], w0 = e0 >> 6, w1 = (e0 + ni - 1) >> 6;
             if (w0 != w1) {
-                float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-                add9(acc, part + ((size_t)w0 * 2 + 1) * 3);
-                for (uint32_t w = w0 + 1; w <= w1; w++) add9(acc, part + ((size_t)w * 2) * 3);
-                write_grads(o, (uint32_t)idx, acc);
+                float acc[NV] = {};
+                add9<NV>(acc, part + ((size_t)w0 * 2 + 1) * 3);
+                for (uint32_t w = w0 + 1; w <= w1; w++) add9<NV>(acc, part + ((size_t)w * 2) * 3);
+                write_grads<NV>(o, (uint32_t)idx, acc);
             }
         }
     }
@@ -186,6 +197,10 @@ __device__ __forceinline__ V3 gaussian_grads(
         dm2.y = (proj[4] * m_w - proj[7] * mul1) * g2x + (proj[5] * m_w - proj[7] * mul2) * g2y;
         dm2.z = (proj[8] * m_w - proj[11] * mul1) * g2x + (proj[9] * m_w - proj[11] * mul2) * g2y;
         dmean = dmean + dm2;
+        if (NV == 10) {  // depth part: W3 times the depth row of the view matrix
+            const float w3 = dc.z;
+            dmean = dmean + v3(view.m[2] * w3, view.m[6] * w3, view.m[10] * w3);
+        }
         // SH part (backward.cu:390-391): added by the caller
         // cov3D part (backward.cu:394-395)
         if (scales) {
@@ -200,10 +215,12 @@ __device__ __forceinline__ V3 gaussian_grads(
     dL_dscale[3 * idx + 1] = dscale.y;
     dL_dscale[3 * idx + 2] = dscale.z;
     reinterpret_cast<float4 *>(dL_drot)[idx] = drot;
+    if (NV == 10) reinterpret_cast<float *>(const_cast<float4 *>(dL_dconic) + idx)[2] = 0.f;  // W3's slot: back to 0
     return dmean;
 }
 
 // Without SH coefficients (colours precomputed): one thread per Gaussian, dL/dmean3D = the two terms.
+template <int NV>
 __global__ __launch_bounds__(256) void gaussian_backward_kernel(
     Args a, GeomState g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
@@ -212,7 +229,7 @@ __global__ __launch_bounds__(256) void gaussian_backward_kernel(
     const uint32_t *__restrict__ e_first, const float4 *__restrict__ part, GradOut o) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.P) return;
-    const V3 dmean = gaussian_grads(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
+    const V3 dmean = gaussian_grads<NV>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
                                     dL_dcov3D, dL_dscale, dL_drot, e_first, part, o);
     dL_dmean3D[3 * idx + 0] = dmean.x;
     dL_dmean3D[3 * idx + 1] = dmean.y;
@@ -230,7 +247,7 @@ __global__ __launch_bounds__(256) void gaussian_backward_kernel(
 // work split at the SH part) cost one launch more.
 constexpr int kShThreads = 128, kShRow = 49;
 
-template <bool kVec4>
+template <bool kVec4, int NV>
 __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     Args a, GeomState g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
@@ -261,7 +278,7 @@ __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     V3 dmean = v3(0, 0, 0);
     const int idx = g0 + threadIdx.x;
     if ((int)threadIdx.x < n)  // pass 2 writes this Gaussian's dL/dcolor (when it spans waves) before it is read
-        dmean = gaussian_grads(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic, dL_dcov3D,
+        dmean = gaussian_grads<NV>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic, dL_dcov3D,
                                dL_dscale, dL_drot, e_first, part, o);
     __syncthreads();
     if ((int)threadIdx.x < n) {
@@ -316,20 +333,33 @@ static uint32_t *scratch_e_first(char *scratch, int R) {
     return (uint32_t *)(scratch + align_up(nw * 2 * 3 * sizeof(float4), 256));
 }
 
-hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+template <int NV>
+static hipError_t contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
                                  float *dL_dcolor, hipStream_t s) {
     if (R == 0) return hipSuccess;  // every Gaussian has n_inst = 0: gaussian_backward writes the zeros
     const size_t nw = ((size_t)R + 63) / 64;
     const uint32_t *n_dev = b.scratch;  // L' (binning.hip)
-    hipLaunchKernelGGL(contrib_segments_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, n_dev, b.gid_by_e,
+    hipLaunchKernelGGL(contrib_segments_kernel<NV>, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, n_dev, b.gid_by_e,
                        reinterpret_cast<const float4 *>(contrib), grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity,
                                                                           dL_dcolor),
                        scratch_part(scratch), scratch_e_first(scratch, R));
     return hipGetLastError();
 }
 
-hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
+hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+                                 char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
+                                 float *dL_dcolor, hipStream_t s) {
+    return contrib_reduce<9>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s);
+}
+hipError_t launch_contrib_reduce_depth(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+                                       char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
+                                       float *dL_dcolor, hipStream_t s) {
+    return contrib_reduce<10>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s);
+}
+
+template <int NV>
+static hipError_t gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
                                     const float *means3D, const float *shs, const float *scales, const float *rotations,
                                     const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
                                     float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
@@ -337,16 +367,34 @@ hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scr
     const GradOut o = grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor);
     if (shs) {
         const bool vec4 = a.M == 16 && (((size_t)shs | (size_t)dL_dsh) & 15) == 0;
-        hipLaunchKernelGGL(vec4 ? gaussian_sh_backward_kernel<true> : gaussian_sh_backward_kernel<false>,
+        const auto kernel = vec4 ? gaussian_sh_backward_kernel<true, NV> : gaussian_sh_backward_kernel<false, NV>;
+        hipLaunchKernelGGL(kernel,
                            dim3((a.P + kShThreads - 1) / kShThreads), dim3(kShThreads), 0, s, a, g, radii, means3D,
                            scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot,
                            scratch_e_first(scratch, R), scratch_part(scratch), o, shs, g.clamped, dL_dcolor, dL_dsh);
     } else {
-        hipLaunchKernelGGL(gaussian_backward_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a, g, radii, means3D,
+        hipLaunchKernelGGL(gaussian_backward_kernel<NV>, dim3((a.P + 255) / 256), dim3(256), 0, s, a, g, radii, means3D,
                            scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D,
                            dL_dscale, dL_drot, scratch_e_first(scratch, R), scratch_part(scratch), o);
     }
     return hipGetLastError();
+}
+hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
+                                    const float *means3D, const float *shs, const float *scales, const float *rotations,
+                                    const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
+                                    float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
+                                    float *dL_dscale, float *dL_drot, hipStream_t s) {
+    return gaussian_backward<9>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic,
+                                dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, s);
+}
+hipError_t launch_gaussian_backward_depth(const Args &a, GeomState g, int R, char *scratch, const int *radii,
+                                          const float *means3D, const float *shs, const float *scales,
+                                          const float *rotations, const float *cov3D, float *dL_dmean2D,
+                                          float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
+                                          hipStream_t s) {
+    return gaussian_backward<10>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic,
+                                 dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, s);
 }
 
 }  // namespace gs4d

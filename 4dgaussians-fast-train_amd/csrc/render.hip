@@ -503,7 +503,10 @@ template <int CTRL>
 __device__ __forceinline__ float dpp(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
 }
-// record float offset (from record j's start; record j + 1 follows at +12) of this lane's total
+// record float offset (from record j's start; record j + 1 follows at +12) of this lane's total.
+// DEPTH: the odd rows of x5, which hold nothing otherwise, carry the depth sum W3 = sum w dL/ddepth to
+// record float 9 (the first of the three free floats after W2).
+template <bool DEPTH>
 __device__ __forceinline__ int red_offset(int lane) {
     const int r = lane >> 4, c = lane & 15, splat = (r >> 1) * 12, odd = r & 1;
     switch (c) {
@@ -511,12 +514,13 @@ __device__ __forceinline__ int red_offset(int lane) {
     case 4: return splat + (odd ? 8 : 7);   // x3: W1, W2
     case 8: return splat + (odd ? 6 : 5);   // x2: S u yl^2, W0
     case 12: return splat + (odd ? 4 : 1);  // x4: S dx u yl, S dx u
-    case 2: return odd ? -1 : splat + 3;    // x5: S dx^2 u (odd rows hold nothing)
+    case 2: return odd ? (DEPTH ? splat + 9 : -1) : splat + 3;  // x5: S dx^2 u (odd rows: W3 or nothing)
     default: return -1;
     }
 }
+template <bool DEPTH>
 __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const SplatPart &b, float dxa, float dxb,
-                                                     float *rec_pair, int lane, int roff) {
+                                                     float w3a, float w3b, float *rec_pair, int lane, int roff) {
     const float h0 = swap32_add(a.u0, b.u0);  // lanes 0-31: a, 32-63: b
     const float h1 = swap32_add(a.u1, b.u1);
     const float h2 = swap32_add(a.u2, b.u2);
@@ -533,7 +537,15 @@ __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const S
     // stage A (c, c ^ 8): x1 | x2 -> z12, x3 | x4 -> z34, x5 -> z5
     const float z12 = (c8 ? x1 : x2) + dpp<0x128>(c8 ? x2 : x1);  // row_ror:8
     const float z34 = (c8 ? x3 : x4) + dpp<0x128>(c8 ? x4 : x3);
-    const float z5 = x5 + dpp<0x128>(x5);
+    float z5 = x5 + dpp<0x128>(x5);
+    if (DEPTH) {
+        // one more swap pair: rows 1 and 3 of x6 hold the column sums of a's and b's W3, which take z5's unused
+        // odd rows from here on (one DPP move more).  They join after x5's own stage A so that the even rows'
+        // arithmetic is the colour-only kernel's to the bit (x5's product and add contract into one fma there).
+        const float x6 = swap16_add(0.f, swap32_add(w3a, w3b));
+        const float z6 = x6 + dpp<0x128>(x6);
+        z5 = (lane & 16) ? z6 : z5;
+    }
     // stage B (half-row mirror): z12 | z34 -> w
     const float w = (c4 ? z12 : z34) + dpp<0x141>(c4 ? z34 : z12);
     const float w5 = z5 + dpp<0x141>(z5);
@@ -548,8 +560,10 @@ __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const S
 // background taken as one more layer behind the last contributor (colour bg, alpha 1): A starts at
 // bg . dL/dpix instead of 0, and T_final / (1 - alpha_i) = T_i prod_{i<j} (1 - alpha_j) follows from
 // the walk's own T -- the same value up to rounding, without a per-pixel constant.
+// dd = dL/ddepth (the depth-gradient instantiation only): the depth image is one more blended channel
+// whose "colour" is the splat's view depth and whose background is 0, so A needs no second accumulator.
 struct BwdPixels {
-    f2 T[2], A[2], dp0[2], dp1[2], dp2[2];
+    f2 T[2], A[2], dp0[2], dp1[2], dp2[2], dd[2];
 };
 
 // One half tile of one splat of the reverse walk: updates the half's pixel state and adds its
@@ -593,11 +607,16 @@ __device__ __forceinline__ HalfAlpha half_alpha(const f2 Y2, const f2 C2, const 
     return h;
 }
 // The rest of a step once the splat's T (the transmittance in front of it, Tn) is known.
-template <bool GEN>
+// DEPTH: diff gains d_g dL/ddepth as its last term (dL/ddepth = 0 leaves every value as it was) and
+// U[6] = W3 accumulates w dL/ddepth.
+template <bool GEN, int NU>
 __device__ __forceinline__ void half_accum(const HalfAlpha &h, const f2 Tn, f2 &A, const f2 dp0, const f2 dp1,
-                                           const f2 dp2, const f2 R2, const f2 G2, const f2 B2, f2 yl, f2 yl2,
-                                           f2 &U0, f2 &U1, f2 &U2, f2 &W0, f2 &W1, f2 &W2) {
-    const f2 diff = fma2(B2, dp2, fma2(G2, dp1, fma2(R2, dp0, -A)));  // c . dL/dpix - accum_rec . dL/dpix
+                                           const f2 dp2, const f2 dd, const f2 R2, const f2 G2, const f2 B2,
+                                           const f2 D2, f2 yl, f2 yl2, f2 (&U)[NU]) {
+    constexpr bool DEPTH = NU == 7;
+    f2 &U0 = U[0], &U1 = U[1], &U2 = U[2], &W0 = U[3], &W1 = U[4], &W2 = U[5];
+    f2 diff = fma2(B2, dp2, fma2(G2, dp1, fma2(R2, dp0, -A)));  // c . dL/dpix - accum_rec . dL/dpix
+    if (DEPTH) diff = fma2(D2, dd, diff);                        // + d_g dL/ddepth
     A = fma2(h.ae, diff, A);                    // accum_rec for the next splat in front
     const f2 w = h.ae * Tn;                     // dchannel_dcolor (backward.cu:521)
     // u' = o G dL/dalpha = o G T diff (backward.cu:519-534, bg term in A's start value); without the
@@ -609,6 +628,7 @@ __device__ __forceinline__ void half_accum(const HalfAlpha &h, const f2 Tn, f2 &
     W0 = fma2(w, dp0, W0);
     W1 = fma2(w, dp1, W1);
     W2 = fma2(w, dp2, W2);
+    if (DEPTH) U[NU - 1] = fma2(w, dd, U[NU - 1]);
 }
 // One half tile of one splat of the reverse walk: updates the half's pixel state and adds its
 // per-lane partial sums (moments of u' = o G dL/dalpha in the tile-centred row coordinate yl -- the
@@ -623,23 +643,24 @@ __device__ __forceinline__ void half_accum(const HalfAlpha &h, const f2 Tn, f2 &
 // a is T / (1 - alpha_a), in front of b T / ((1 - alpha_a)(1 - alpha_b)) -- one v_rcp_f32 of the
 // product per pixel (8 issue cycles each) and two multiplies instead of two reciprocals.
 struct SplatOps {
-    f2 Y2, C2, O2, R2, G2, B2, pa2, pb2;
+    f2 Y2, C2, O2, R2, G2, B2, D2, pa2, pb2;  // D2 = the view depth (read by the depth-gradient walk only)
     bool chk;
     uint32_t contributor;
 };
-template <bool ALL, bool GEN>
-__device__ __forceinline__ void half_step(f2 &T, f2 &A, const f2 dp0, const f2 dp1, const f2 dp2, const SplatOps &s,
-                                          f2 yl, f2 yl2, uint32_t last0, uint32_t last1, f2 (&U)[6]) {
+template <bool ALL, bool GEN, int NU>
+__device__ __forceinline__ void half_step(f2 &T, f2 &A, const f2 dp0, const f2 dp1, const f2 dp2, const f2 dd,
+                                          const SplatOps &s, f2 yl, f2 yl2, uint32_t last0, uint32_t last1,
+                                          f2 (&U)[NU]) {
     const HalfAlpha h = half_alpha<ALL, GEN>(s.Y2, s.C2, s.O2, s.pa2, s.pb2, yl, s.chk, s.contributor, last0, last1);
     const f2 inv = f2{__builtin_amdgcn_rcpf(h.om.x), __builtin_amdgcn_rcpf(h.om.y)};
     const f2 Tn = T * inv;  // backward.cu:503
     T = Tn;
-    half_accum<GEN>(h, Tn, A, dp0, dp1, dp2, s.R2, s.G2, s.B2, yl, yl2, U[0], U[1], U[2], U[3], U[4], U[5]);
+    half_accum<GEN>(h, Tn, A, dp0, dp1, dp2, dd, s.R2, s.G2, s.B2, s.D2, yl, yl2, U);
 }
-template <bool ALL, bool GEN>
-__device__ __forceinline__ void half_pair_step(f2 &T, f2 &A, const f2 dp0, const f2 dp1, const f2 dp2,
+template <bool ALL, bool GEN, int NU>
+__device__ __forceinline__ void half_pair_step(f2 &T, f2 &A, const f2 dp0, const f2 dp1, const f2 dp2, const f2 dd,
                                                const SplatOps &sa, const SplatOps &sb, f2 yl, f2 yl2, uint32_t last0,
-                                               uint32_t last1, f2 (&Ua)[6], f2 (&Ub)[6]) {
+                                               uint32_t last1, f2 (&Ua)[NU], f2 (&Ub)[NU]) {
     const HalfAlpha ha = half_alpha<ALL, GEN>(sa.Y2, sa.C2, sa.O2, sa.pa2, sa.pb2, yl, sa.chk, sa.contributor,
                                               last0, last1);
     const HalfAlpha hb = half_alpha<ALL, GEN>(sb.Y2, sb.C2, sb.O2, sb.pa2, sb.pb2, yl, sb.chk, sb.contributor,
@@ -648,19 +669,23 @@ __device__ __forceinline__ void half_pair_step(f2 &T, f2 &A, const f2 dp0, const
     const f2 r = f2{__builtin_amdgcn_rcpf(prod.x), __builtin_amdgcn_rcpf(prod.y)};
     const f2 Tb = T * r;         // backward.cu:503 twice: T / (1 - alpha_a) / (1 - alpha_b)
     const f2 Ta = Tb * hb.om;    // T / (1 - alpha_a)
-    half_accum<GEN>(ha, Ta, A, dp0, dp1, dp2, sa.R2, sa.G2, sa.B2, yl, yl2, Ua[0], Ua[1], Ua[2], Ua[3], Ua[4], Ua[5]);
-    half_accum<GEN>(hb, Tb, A, dp0, dp1, dp2, sb.R2, sb.G2, sb.B2, yl, yl2, Ub[0], Ub[1], Ub[2], Ub[3], Ub[4], Ub[5]);
+    half_accum<GEN>(ha, Ta, A, dp0, dp1, dp2, dd, sa.R2, sa.G2, sa.B2, sa.D2, yl, yl2, Ua);
+    half_accum<GEN>(hb, Tb, A, dp0, dp1, dp2, dd, sb.R2, sb.G2, sb.B2, sb.D2, yl, yl2, Ub);
     T = Tb;
 }
 
+constexpr int kBwdDepthWaves = 4;  // waves per SIMD of the depth-gradient instantiation (<= 128 VGPRs)
 // 4 waves per SIMD (<= 128 VGPRs, no spills): the reach-combo blocks hold at most the four falloff chains
-// of one pair.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void render_backward_kernel(Args a, const uint2 *__restrict__ ranges, const uint32_t *__restrict__ order,
+// of one pair.  DEPTH (gs4d_backward_depth): dL/ddepth joins the walk as a fourth channel; its extra
+// per-pixel state, operands and sums are kBwdDepthWaves's business.
+template <bool DEPTH>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwdDepthWaves : 4, DEPTH ? kBwdDepthWaves : 4))) void render_backward_kernel(Args a, const uint2 *__restrict__ ranges, const uint32_t *__restrict__ order,
                             const uint32_t *__restrict__ gid_by_e,
                             const uint32_t *__restrict__ upos, const float4 *__restrict__ splat,
                             const float *__restrict__ final_Ts,
                             const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpixels,
-                            float *__restrict__ contrib) {
+                            const float *__restrict__ dL_ddepths, float *__restrict__ contrib) {
+    constexpr int NU = DEPTH ? 7 : 6;
     __shared__ SplatLDS s_sp[64];
     __shared__ float4 s_rec[64][3];  // reduced sums of the batch's splats
     const int tile = (int)__builtin_amdgcn_readfirstlane(order[blockIdx.x]);  // longest runs first
@@ -680,7 +705,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const f2 yl[2] = {f2{ylane, ylane + 4.f}, f2{ylane + 8.f, ylane + 12.f}};
     const f2 yl2[2] = {yl[0] * yl[0], yl[1] * yl[1]};
     const float yc = (float)(ty * kBlockY) + 7.5f;
-    const int roff = red_offset(lane);
+    const int roff = red_offset<DEPTH>(lane);
 
     BwdPixels st;
     uint32_t lastc[4];
@@ -695,14 +720,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const float d0 = inside ? dL_dpixels[pix] : 0.f;
         const float d1 = inside ? dL_dpixels[HW + pix] : 0.f;
         const float d2 = inside ? dL_dpixels[2 * HW + pix] : 0.f;
+        const float d3 = (DEPTH && inside) ? dL_ddepths[pix] : 0.f;
         lastc[k] = inside ? n_contrib[pix] : 0u;
         inside_m[k] = ballot(inside);
         const float a0 = bg.x * d0 + bg.y * d1 + bg.z * d2;  // the background layer behind the last splat
         const int h = k >> 1;
         if (k & 1) {
             st.T[h].y = tf; st.dp0[h].y = d0; st.dp1[h].y = d1; st.dp2[h].y = d2; st.A[h].y = a0;
+            st.dd[h].y = d3;
         } else {
             st.T[h].x = tf; st.dp0[h].x = d0; st.dp1[h].x = d1; st.dp2[h].x = d2; st.A[h].x = a0;
+            st.dd[h].x = d3;
         }
         max_last = max(max_last, lastc[k]);
         if (inside) min_last = min(min_last, lastc[k]);
@@ -798,31 +826,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 pa[i] = fmaf(geo[i].z * dxs[i], dxs[i], opc[i].y);  // forward: fmaf(geo.z dx, dx, lo), geo.w dx
                 pb[i] = geo[i].w * dxs[i];
             }
-            f2 U[2][6];
+            f2 U[2][NU];
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
-                for (int k = 0; k < 6; k++) U[i][k] = bc2(0.f);
+                for (int k = 0; k < NU; k++) U[i][k] = bc2(0.f);
             SplatOps so[2];
 #pragma unroll
             for (int i = 0; i < 2; i++)
                 so[i] = SplatOps{bc2(geo[i].y), bc2(opc[i].x), bc2(opc[i].w), bc2(col[i].x), bc2(col[i].y),
-                                 bc2(col[i].z), bc2(pa[i]), bc2(pb[i]), ((nonpd >> (j + i)) & 1) != 0,
+                                 bc2(col[i].z), bc2(col[i].w), bc2(pa[i]), bc2(pb[i]), ((nonpd >> (j + i)) & 1) != 0,
                                  (uint32_t)(end - 1 - (j + i))};
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 if (M[h] == 3)
-                    half_pair_step<ALL, GEN>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], so[0], so[1], yl[h],
-                                             yl2[h], lastc[2 * h], lastc[2 * h + 1], U[0], U[1]);
+                    half_pair_step<ALL, GEN>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], st.dd[h], so[0], so[1],
+                                             yl[h], yl2[h], lastc[2 * h], lastc[2 * h + 1], U[0], U[1]);
                 else if (M[h] != 0)
-                    half_step<ALL, GEN>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], so[M[h] >> 1], yl[h],
-                                        yl2[h], lastc[2 * h], lastc[2 * h + 1], U[M[h] >> 1]);
+                    half_step<ALL, GEN>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], st.dd[h], so[M[h] >> 1],
+                                        yl[h], yl2[h], lastc[2 * h], lastc[2 * h + 1], U[M[h] >> 1]);
             }
 #pragma unroll
             for (int i = 0; i < 2; i++)
                 part[i] = SplatPart{hsum(U[i][0]), hsum(U[i][1]), hsum(U[i][2]), hsum(U[i][3]), hsum(U[i][4]),
                                     hsum(U[i][5])};
-            wave_sum_pair_to_lds(part[0], part[1], dxs[0], dxs[1], reinterpret_cast<float *>(s_rec[j]), lane, roff);
+            wave_sum_pair_to_lds<DEPTH>(part[0], part[1], dxs[0], dxs[1], DEPTH ? hsum(U[0][NU - 1]) : 0.f,
+                                        DEPTH ? hsum(U[1][NU - 1]) : 0.f, reinterpret_cast<float *>(s_rec[j]), lane,
+                                        roff);
         };
         using I3 = std::integral_constant<int, 3>;
         auto walk_batch = [&](auto all) {
@@ -866,7 +896,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             const float4 r0 = s_rec[lane][0], r1 = s_rec[lane][1], r2 = s_rec[lane][2];
             const float my_l = s_sp[lane].geo.y;  // this lane's splat, my - yc
             const float io = s_sp[lane].opc.z;    // 1 / o: the moments were taken on u' = o u
-            // r0 = (S u, S dx u, S u yl, S dx^2 u), r1 = (S dx u yl, S u yl^2, W0, W1), r2 = (W2, -, -, -)
+            // r0 = (S u, S dx u, S u yl, S dx^2 u), r1 = (S dx u yl, S u yl^2, W0, W1), r2 = (W2, W3 or -, -, -)
             const float s_u = r0.x, s_uyl = r0.z;
             const float v2 = my_l * s_u - s_uyl;                 // S u dy
             const float v4 = my_l * r0.y - r1.x;                 // S dx u dy
@@ -884,8 +914,17 @@ hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gi
                                   hipStream_t s) {
     const int T = a.gx * a.gy;
     (void)colors;  // the splat records hold the colours the forward blended (colors_precomp or SH)
-    hipLaunchKernelGGL(render_backward_kernel, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e, upos,
-                       g.splat, img.final_T, img.n_contrib, dL_dpix, contrib);
+    hipLaunchKernelGGL(render_backward_kernel<false>, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e,
+                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, contrib);
+    return hipGetLastError();
+}
+// the same walk with dL/ddepth (H x W): every record also carries W3 in float 9
+hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
+                                        ImageState img, const float *dL_dpix, const float *dL_ddepth, float *contrib,
+                                        hipStream_t s) {
+    const int T = a.gx * a.gy;
+    hipLaunchKernelGGL(render_backward_kernel<true>, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e,
+                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, contrib);
     return hipGetLastError();
 }
 

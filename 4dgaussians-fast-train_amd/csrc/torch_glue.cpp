@@ -120,10 +120,11 @@ RasterizeGaussians(const torch::Tensor &background, const torch::Tensor &means3D
     return std::make_tuple(rendered, out_color, out_depth, radii, geomBuffer, binningBuffer, imgBuffer);
 }
 
-// rasterize_points.cu:119-198
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-           torch::Tensor>
-RasterizeGaussiansBackward(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
+// rasterize_points.cu:119-198; dL_dout_depth != nullptr: the depth-gradient backward (gs4d_backward_depth)
+using BackwardTuple = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+                                 torch::Tensor, torch::Tensor, torch::Tensor>;
+static BackwardTuple
+BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
                            const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
                            const float scale_modifier, const torch::Tensor &cov3D_precomp,
                            const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix, const float tan_fovx,
@@ -155,25 +156,72 @@ RasterizeGaussiansBackward(const torch::Tensor &background, const torch::Tensor 
              cp = prep(campos, "campos", dev);
         int vt = 0;
         auto vm = prep_view(viewmatrix, dev, vt);
+        torch::Tensor dd;
+        if (dL_dout_depth) {
+            if (dL_dout_depth->numel() != (long long)H * W)
+                throw std::runtime_error("grad_out_depth must have H * W elements");
+            dd = prep(*dL_dout_depth, "grad_out_depth", dev);
+        }
         torch::Tensor rad = radii.contiguous();
         if (rad.numel() && (rad.scalar_type() != torch::kInt32 || !rad.is_cuda()))
             throw std::runtime_error("radii must be an int32 GPU tensor");
         torch::Tensor scratch = torch::empty({0}, means3D.options().dtype(torch::kByte));
         Resizer rs{&scratch};
         hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
-        int st = gs4d_backward_ex(
-            P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
-            fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad.numel() ? rad.data_ptr<int>() : nullptr,
-            reinterpret_cast<char *>(geomBuffer.data_ptr()),
-            binningBuffer.numel() ? reinterpret_cast<char *>(binningBuffer.data_ptr()) : nullptr,
-            reinterpret_cast<char *>(imageBuffer.data_ptr()), fptr(dl), dL_dmeans2D.data_ptr<float>(), nullptr,
-            dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
-            dL_dcov3D.data_ptr<float>(), M ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(),
-            dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
-        check_status(st, "rasterize_gaussians_backward");
+        const int *rad_ptr = rad.numel() ? rad.data_ptr<int>() : nullptr;
+        char *geom = reinterpret_cast<char *>(geomBuffer.data_ptr());
+        char *binning = binningBuffer.numel() ? reinterpret_cast<char *>(binningBuffer.data_ptr()) : nullptr;
+        char *image = reinterpret_cast<char *>(imageBuffer.data_ptr());
+        float *dsh = M ? dL_dsh.data_ptr<float>() : nullptr;
+        int st;
+        if (dL_dout_depth)
+            st = gs4d_backward_depth(
+                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
+                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
+                fptr(dd), dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(),
+                dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), dsh,
+                dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0,
+                (void *)stream, vt);
+        else
+            st = gs4d_backward_ex(
+                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
+                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
+                dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
+                dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(),
+                dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
+        check_status(st, dL_dout_depth ? "rasterize_gaussians_backward_depth" : "rasterize_gaussians_backward");
     }
     return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
                            dL_drotations);
+}
+
+BackwardTuple
+RasterizeGaussiansBackward(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
+                           const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
+                           const float scale_modifier, const torch::Tensor &cov3D_precomp,
+                           const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix, const float tan_fovx,
+                           const float tan_fovy, const torch::Tensor &dL_dout_color, const torch::Tensor &sh,
+                           const int degree, const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
+                           const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug) {
+    return BackwardImpl(nullptr, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                        viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                        binningBuffer, imageBuffer, debug);
+}
+
+// the same with the depth image's gradient (1, H, W) or (H, W) after dL_dout_color: gs4d_backward_depth
+BackwardTuple
+RasterizeGaussiansBackwardDepth(const torch::Tensor &background, const torch::Tensor &means3D,
+                                const torch::Tensor &radii, const torch::Tensor &colors, const torch::Tensor &scales,
+                                const torch::Tensor &rotations, const float scale_modifier,
+                                const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+                                const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy,
+                                const torch::Tensor &dL_dout_color, const torch::Tensor &dL_dout_depth,
+                                const torch::Tensor &sh, const int degree, const torch::Tensor &campos,
+                                const torch::Tensor &geomBuffer, const int R, const torch::Tensor &binningBuffer,
+                                const torch::Tensor &imageBuffer, const bool debug) {
+    return BackwardImpl(&dL_dout_depth, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
+                        geomBuffer, R, binningBuffer, imageBuffer, debug);
 }
 
 // rasterize_points.cu:200-219
@@ -231,6 +279,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians", &RasterizeGaussians);
     m.def("debug_pair_alpha", &DebugPairAlpha);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
+    m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });
     m.def("last_timings", &last_timings);

@@ -8,7 +8,9 @@ Public surface identical to the reference package
   rasterize_gaussians            functional entry (:21-42)
   _RasterizeGaussians            torch.autograd.Function (:44-155)
 
-so gaussian_renderer/__init__.py and train.py run unchanged.  The compute runs in libgs4d (HIP
+so gaussian_renderer/__init__.py and train.py run unchanged.  One opt-in extension, off by default:
+depth_grad=True (rasterize_gaussians, GaussianRasterizer) selects _RasterizeGaussiansDepth, whose backward
+also back-propagates the depth image's gradient, which the reference drops (:100-101).  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
 without the built extension raises ImportError -- there is no CPU fallback.
 """
@@ -19,7 +21,8 @@ import torch.nn as nn
 
 from . import _C  # noqa: F401  (fails loudly when the HIP extension is missing)
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
+           "_RasterizeGaussiansDepth"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -56,9 +59,10 @@ def _invoke(fn, args, debug, dump_name, stage):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                        raster_settings, depth_grad=False):
+    fn = _RasterizeGaussiansDepth if depth_grad else _RasterizeGaussians
+    return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                    raster_settings)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -100,15 +104,42 @@ class _RasterizeGaussians(torch.autograd.Function):
         return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
 
 
+class _RasterizeGaussiansDepth(torch.autograd.Function):
+    """_RasterizeGaussians whose backward also takes the depth image's gradient (opt-in: depth_grad=True)."""
+
+    forward = staticmethod(_RasterizeGaussians.forward)  # identical: same launches, same saved tensors
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth):
+        s = ctx.raster_settings
+        if grad_out_color is None and grad_depth is None:
+            return (None,) * 9
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
+         img_buf) = ctx.saved_tensors
+        H, W = s.image_height, s.image_width
+        if grad_out_color is None:
+            grad_out_color = torch.zeros((3, H, W), dtype=torch.float32, device=means3D.device)
+        if grad_depth is None:
+            grad_depth = torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device)
+        # _C.rasterize_gaussians_backward's positional order with grad_depth after grad_out_color
+        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, grad_depth, sh, s.sh_degree,
+                s.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
+        (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _invoke(
+            _C.rasterize_gaussians_backward_depth, args, s.debug, "snapshot_bw.dump", "backward")
+        return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+
+
 def _empty_if_none(t):
     # "not provided" travels as an empty tensor (reference :197-207)
     return torch.Tensor([]) if t is None else t
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    def __init__(self, raster_settings, depth_grad=False):
         super().__init__()
         self.raster_settings = raster_settings
+        self.depth_grad = depth_grad  # opt-in: the depth image's gradient flows back (_RasterizeGaussiansDepth)
 
     def markVisible(self, positions):
         """Near-plane visibility mask of `positions` for this camera (reference :176-185)."""
@@ -126,4 +157,4 @@ class GaussianRasterizer(nn.Module):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, _empty_if_none(shs), _empty_if_none(colors_precomp), opacities,
                                    _empty_if_none(scales), _empty_if_none(rotations), _empty_if_none(cov3D_precomp),
-                                   self.raster_settings)
+                                   self.raster_settings, depth_grad=self.depth_grad)

@@ -100,7 +100,9 @@ class RenderPackage(dict):
         return dict.__len__(self)
 
 
-def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine"):
+def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False):
+    """depth_grad=True (this build's opt-in): the gradient of the returned "depth" flows back through the
+    rasterizer; by default it is dropped, as in the reference."""
     xyz = pc.get_xyz
     # the rasterizer's means2D gradient sink (:24-29 builds zeros + 0 and retains its grad; a zero leaf
     # holds the same values and receives the same .grad)
@@ -119,7 +121,7 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
     # torch.tensor(time).to(dev).repeat(P, 1) (:52): the same float32 column, as one device value broadcast
     # over the P rows (made once per (device, time); no fill per call)
     time = _time_value(_time_float(viewpoint_camera.time), dev).expand(xyz.shape[0], 1)
-    rasterizer = dgr.GaussianRasterizer(raster_settings=settings)
+    rasterizer = dgr.GaussianRasterizer(raster_settings=settings, depth_grad=depth_grad)
     if "coarse" not in stage and "fine" not in stage:
         raise NotImplementedError(stage)
     if getattr(pc, "fused", False) and getattr(pc, "fused_tail", True) and xyz.is_cuda:

@@ -10,6 +10,10 @@ and the NaN check that re-execs the program (:255-257) are not part of a trainin
 With `data_parallel=True` the views of the batch are sharded over the torch.distributed ranks
 (gs4d_train.dp): each rank renders its share, and the parameter gradients, viewspace gradients,
 radii and visibility are reduced so every replica takes the single-process step.
+
+Depth supervision (this build's opt-in, no reference counterpart): with opt.lambda_depth != 0 a view given as
+(camera, gt_image, gt_depth) adds lambda_depth * mean over the valid pixels (gt_depth > 0) of
+|depth - gt_depth| to the loss, and is rendered with depth_grad=True so the term reaches the Gaussians.
 """
 import torch
 
@@ -17,9 +21,19 @@ from . import dp
 from .losses import l1_loss_torch
 
 
+def depth_l1(depth, gt_depth):
+    """(sum over the valid pixels of |depth - gt_depth|, masked difference, number of valid pixels (>= 1));
+    gt_depth is (1, H, W) or (H, W), a pixel is valid where gt_depth > 0"""
+    gt = gt_depth.reshape(depth.shape)
+    valid = gt > 0
+    diff = torch.where(valid, depth - gt, torch.zeros_like(depth))
+    return diff.abs().sum(), diff, valid.sum().clamp(min=1)
+
+
 def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine", fused_loss=None,
                data_parallel=False, render_fn=None):
-    """views: list of (camera, gt_image (3, H, W)).  Returns the (detached) batch loss tensor.
+    """views: list of (camera, gt_image (3, H, W)) or (camera, gt_image, gt_depth (1, H, W) or (H, W)); the
+    depth is read only when opt.lambda_depth != 0.  Returns the (detached) batch loss tensor.
 
     render_fn(camera, gaussians, debug, bg, stage=...) -> render()'s dict; defaults to
     gs4d_train.render.render (the HIP rasterizer).  The multi-process CPU tests pass a torch stand-in."""
@@ -31,9 +45,16 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
         gaussians.oneupSHdegree()
     mine = dp.shard_views(len(views)) if data_parallel else list(range(len(views)))
     images, gts, radii_list, vis_list, vs_list = [], [], [], [], []
+    lambda_depth = getattr(opt, "lambda_depth", 0.0)
+    depths, gt_depths = [], []  # of the views that carry a gt depth, when lambda_depth != 0
     for v in mine:
-        cam, gt = views[v]
-        pkg = render_fn(cam, gaussians, False, background, stage=stage)
+        cam, gt = views[v][0], views[v][1]
+        if lambda_depth != 0 and len(views[v]) > 2:
+            pkg = render_fn(cam, gaussians, False, background, stage=stage, depth_grad=True)
+            depths.append(pkg["depth"])
+            gt_depths.append(views[v][2])
+        else:
+            pkg = render_fn(cam, gaussians, False, background, stage=stage)
         images.append(pkg["render"].unsqueeze(0))
         gts.append(gt.unsqueeze(0))
         radii_list.append(pkg["radii"].unsqueeze(0))
@@ -80,6 +101,22 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
             loss = Ll1 * share if data_parallel else Ll1
     else:
         loss = torch.zeros((), device=dev)
+    depth_grads = None
+    if depths:
+        # lambda_depth * (batch mean over this rank's views of the per-view valid-pixel mean) * share, like the L1
+        scale = lambda_depth * share / len(mine)
+        if image_grad is not None:
+            # fused path: the term's value and its gradient formed explicitly (one H x W pass per view in torch)
+            depth_grads = []
+            with torch.no_grad():
+                for d, gd in zip(depths, gt_depths):
+                    total, diff, n = depth_l1(d, gd)
+                    loss = loss + total / n * scale
+                    depth_grads.append(torch.sign(diff) * (scale / n))
+        else:
+            for d, gd in zip(depths, gt_depths):
+                total, _, n = depth_l1(d, gd)
+                loss = loss + total / n * scale
     reg_w = (hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight)
     reg_scale = 1.0 / dp.world() if data_parallel else 1.0
     reg_deferred = False
@@ -98,7 +135,10 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     # a data-parallel rank with no view of the batch (len(views) < world) and no regulariser has a
     # constant loss: nothing to back-propagate, its gradients are the zeros filled in below
     if image_grad is not None:
-        if image_tensor.requires_grad:
+        if image_tensor.requires_grad and depth_grads:
+            # one backward pass: each view's rasterizer backward takes its colour and depth gradients together
+            torch.autograd.backward([image_tensor] + depths, [image_grad] + depth_grads)
+        elif image_tensor.requires_grad:
             image_tensor.backward(image_grad)
     elif loss.requires_grad:
         loss.backward()

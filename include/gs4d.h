@@ -101,7 +101,28 @@ int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int wi
                      float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
                      int view_transposed);
 
-/* Replaces SimpleKNN::knn (submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
+/* gs4d_backward_ex with a gradient for the depth image (no reference counterpart; opt-in).  The reference
+ * blends a depth image D = sum depth_i alpha_i T_i next to the colour (forward.cu:250,359,377; no background
+ * term) and drops its gradient: _RasterizeGaussians.backward ignores grad_depth
+ * (diff_gaussian_rasterization/__init__.py:100-101).  Here dL_ddepth (H * W floats, the gradient of
+ * out_depth) is back-propagated as a fourth blended channel whose per-splat "colour" is the view depth:
+ * it reaches dL_dopacity, dL_dmean2D, dL_dconic (hence dL_dcov3D, dL_dscale, dL_drot) and dL_dmean3D through
+ * the formulas of the colour channels, and dL_dmean3D also takes (sum over pixels of alpha T dL_ddepth) times
+ * the view matrix's depth row.  dL_dcolor and dL_dsh receive nothing from it.  dL_ddepth = 0 gives
+ * gs4d_backward_ex's results bit for bit, and the results are bitwise repeatable like its own.
+ * Status: GS4D_ERR_ARG for P < 0 or R < 0; GS4D_OK at once for P == 0; GS4D_ERR_ARG when dL_ddepth or
+ * dL_dpix is NULL; everything else as gs4d_backward_ex. */
+int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int width, int height,
+                        const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                        float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                        const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                        float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                        const float *dL_dpix, const float *dL_ddepth, float *dL_dmean2D, float *dL_dconic,
+                        float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
+                        float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug,
+                        void *stream, int view_transposed);
+
+/* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.
  * points: P x 3 fp32 (device, contiguous).  mean_dists[i] = mean of the squared distances from point i

@@ -326,17 +326,18 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
 }  // extern "C"
 
 // gs4d_backward_ex (DEPTH = false) and gs4d_backward_depth (DEPTH = true): the same orchestration over the
-// colour-only or the depth-gradient instantiations of the three backward stages.
+// colour-only or the depth-gradient instantiations of the three backward stages.  dL_dalpha (gs4d_backward_aux;
+// NULL for none) only changes the start value of the reverse walk's running sum, in either instantiation.
 template <bool DEPTH>
 static int backward_impl(int P, int D, int M, int R, const float *background, int width, int height,
                          const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
                          float scale_modifier, const float *rotations, const float *cov3D_precomp,
                          const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
                          float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
-                         const float *dL_dpix, const float *dL_ddepth, float *dL_dmean2D, float *dL_dconic,
-                         float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
-                         float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug,
-                         void *stream_, int view_transposed) {
+                         const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
+                         float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                         float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc,
+                         void *scratch_ctx, int debug, void *stream_, int view_transposed) {
     hipStream_t stream = (hipStream_t)stream_;
     if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "backward: bad sizes");
     if (P == 0) return GS4D_OK;
@@ -373,10 +374,10 @@ static int backward_impl(int P, int D, int M, int R, const float *background, in
         const float *color_ptr = colors_precomp;  // NULL -> the forward's rgb (rasterizer_impl.cu:392)
         if (DEPTH)
             GS4D_REPEATED_STAGE("render_backward", launch_render_backward_depth(a, g, b.gid_by_e, b.upos, img, dL_dpix,
-                                                                                dL_ddepth, contrib, stream));
+                                                                                dL_ddepth, dL_dalpha, contrib, stream));
         else
             GS4D_REPEATED_STAGE("render_backward", launch_render_backward(a, g, b.gid_by_e, b.upos, img, color_ptr,
-                                                                          dL_dpix, contrib, stream));
+                                                                          dL_dpix, dL_dalpha, contrib, stream));
     }
     const float *cov3D_ptr = cov3D_precomp ? cov3D_precomp : g.cov3D;  // rasterizer_impl.cu:414
     if (DEPTH) {
@@ -413,9 +414,9 @@ int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int wi
                      int view_transposed) {
     return backward_impl<false>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
                                 scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, dL_dmean2D,
-                                dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                                scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+                                tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, nullptr,
+                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
 }
 
 int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int width, int height,
@@ -429,9 +430,41 @@ int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int
                         void *stream, int view_transposed) {
     return backward_impl<true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                               tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dmean2D,
-                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                               scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+                               tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, nullptr,
+                               dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                               dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+}
+
+int gs4d_backward_aux(int P, int D, int M, int R, const float *background, int width, int height,
+                      const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                      float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                      const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                      float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                      const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
+                      float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                      float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
+                      int debug, void *stream, int view_transposed) {
+    if (dL_ddepth)
+        return backward_impl<true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                                   tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth,
+                                   dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                   dL_dscale, dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+    // no depth gradient: the colour-only instantiations of the three stages
+    return backward_impl<false>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                                tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, dL_dalpha,
+                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+}
+
+int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out_alpha, void *stream) {
+    if (width <= 0 || height <= 0 || !image_buffer || !out_alpha)
+        return fail(GS4D_ERR_ARG, "alpha_image: the image must be non-empty and both buffers given");
+    // gs4d_forward_ex launches the blend for every P > 0, num_rendered == 0 included, so final_T is always there
+    ImageState img = ImageState::carve(const_cast<char *>(image_buffer), width, height);
+    GS4D_HIP(launch_alpha_image(img, (size_t)width * height, out_alpha, (hipStream_t)stream));
+    return GS4D_OK;
 }
 
 int gs4d_forward(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,

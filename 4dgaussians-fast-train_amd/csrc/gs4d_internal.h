@@ -200,12 +200,16 @@ hipError_t launch_render_forward(const Args &a, GeomState g, BinningState b, Ima
 hipError_t launch_pair_alpha(GeomState g, int n, const int *gid, const int *px, const int *py, float *og, float *pw,
                              hipStream_t s);
 hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos, ImageState img,
-                                  const float *colors, const float *dL_dpix, float *contrib, hipStream_t s);
+                                  const float *colors, const float *dL_dpix, const float *dL_dalpha, float *contrib,
+                                  hipStream_t s);
 // the depth-gradient backward (gs4d_backward_depth): the same three stages with dL/ddepth; the records' float 9
 // carries W3 = sum w dL/ddepth, whose per-Gaussian sum travels in dL_dconic's unused .z slot
+// dL_dalpha (both walks; NULL for none): the gradient of the alpha image 1 - T_final (gs4d_backward_aux)
 hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                        ImageState img, const float *dL_dpix, const float *dL_ddepth, float *contrib,
-                                        hipStream_t s);
+                                        ImageState img, const float *dL_dpix, const float *dL_ddepth,
+                                        const float *dL_dalpha, float *contrib, hipStream_t s);
+// out_alpha[pix] = 1 - final_T[pix] over the n = W * H pixels of the forward's image state (gs4d_alpha_image)
+hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStream_t s);
 hipError_t launch_contrib_reduce_depth(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                        char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
                                        float *dL_dcolor, hipStream_t s);

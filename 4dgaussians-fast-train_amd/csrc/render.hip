@@ -684,7 +684,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
                             const uint32_t *__restrict__ upos, const float4 *__restrict__ splat,
                             const float *__restrict__ final_Ts,
                             const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpixels,
-                            const float *__restrict__ dL_ddepths, float *__restrict__ contrib) {
+                            const float *__restrict__ dL_ddepths, const float *__restrict__ dL_dalphas,
+                            float *__restrict__ contrib) {
     constexpr int NU = DEPTH ? 7 : 6;
     __shared__ SplatLDS s_sp[64];
     __shared__ float4 s_rec[64][3];  // reduced sums of the batch's splats
@@ -723,7 +724,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
         const float d3 = (DEPTH && inside) ? dL_ddepths[pix] : 0.f;
         lastc[k] = inside ? n_contrib[pix] : 0u;
         inside_m[k] = ballot(inside);
-        const float a0 = bg.x * d0 + bg.y * d1 + bg.z * d2;  // the background layer behind the last splat
+        // dL/dalpha of the alpha image 1 - T_final (gs4d_backward_aux; NULL, a wave-uniform test, for none):
+        // d(1 - T_final)/dalpha_i = T_final / (1 - alpha_i) is the background layer's factor with colour -1
+        const float dA = (dL_dalphas && inside) ? dL_dalphas[pix] : 0.f;
+        const float a0 = (bg.x * d0 + bg.y * d1 + bg.z * d2) - dA;  // the background layer behind the last splat
         const int h = k >> 1;
         if (k & 1) {
             st.T[h].y = tf; st.dp0[h].y = d0; st.dp1[h].y = d1; st.dp2[h].y = d2; st.A[h].y = a0;
@@ -909,22 +913,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
     }
 }
 
+// dL_dalpha (H x W, or NULL for none): the alpha image's gradient (gs4d_backward_aux)
 hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                  ImageState img, const float *colors, const float *dL_dpix, float *contrib,
-                                  hipStream_t s) {
+                                  ImageState img, const float *colors, const float *dL_dpix, const float *dL_dalpha,
+                                  float *contrib, hipStream_t s) {
     const int T = a.gx * a.gy;
     (void)colors;  // the splat records hold the colours the forward blended (colors_precomp or SH)
     hipLaunchKernelGGL(render_backward_kernel<false>, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e,
-                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, contrib);
+                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, dL_dalpha, contrib);
     return hipGetLastError();
 }
 // the same walk with dL/ddepth (H x W): every record also carries W3 in float 9
 hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                        ImageState img, const float *dL_dpix, const float *dL_ddepth, float *contrib,
-                                        hipStream_t s) {
+                                        ImageState img, const float *dL_dpix, const float *dL_ddepth,
+                                        const float *dL_dalpha, float *contrib, hipStream_t s) {
     const int T = a.gx * a.gy;
     hipLaunchKernelGGL(render_backward_kernel<true>, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e,
-                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, contrib);
+                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha, contrib);
+    return hipGetLastError();
+}
+
+// gs4d_alpha_image: the accumulated alpha A = sum alpha_i T_i = 1 - T_final of every pixel, from the final_T the
+// forward stored (forward.cu:373; tiles with an empty list included, T = 1).  One streaming pass: n = W * H.
+__global__ __launch_bounds__(256) void alpha_image_kernel(size_t n, const float *__restrict__ final_T,
+                                                          float *__restrict__ out_alpha) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out_alpha[i] = 1.f - final_T[i];
+}
+hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStream_t s) {
+    hipLaunchKernelGGL(alpha_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, img.final_T,
+                       out_alpha);
     return hipGetLastError();
 }
 

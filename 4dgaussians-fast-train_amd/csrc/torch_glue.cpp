@@ -120,11 +120,13 @@ RasterizeGaussians(const torch::Tensor &background, const torch::Tensor &means3D
     return std::make_tuple(rendered, out_color, out_depth, radii, geomBuffer, binningBuffer, imgBuffer);
 }
 
-// rasterize_points.cu:119-198; dL_dout_depth != nullptr: the depth-gradient backward (gs4d_backward_depth)
+// rasterize_points.cu:119-198; dL_dout_depth != nullptr: the depth-gradient backward (gs4d_backward_depth);
+// dL_dout_alpha != nullptr: gs4d_backward_aux, where an empty tensor for either image means "no such gradient"
 using BackwardTuple = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
                                  torch::Tensor, torch::Tensor, torch::Tensor>;
 static BackwardTuple
-BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
+BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_alpha, const torch::Tensor &background,
+             const torch::Tensor &means3D, const torch::Tensor &radii,
                            const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
                            const float scale_modifier, const torch::Tensor &cov3D_precomp,
                            const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix, const float tan_fovx,
@@ -156,11 +158,16 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor &background
              cp = prep(campos, "campos", dev);
         int vt = 0;
         auto vm = prep_view(viewmatrix, dev, vt);
-        torch::Tensor dd;
-        if (dL_dout_depth) {
+        torch::Tensor dd, da;
+        if (dL_dout_depth && !(dL_dout_alpha && dL_dout_depth->numel() == 0)) {
             if (dL_dout_depth->numel() != (long long)H * W)
                 throw std::runtime_error("grad_out_depth must have H * W elements");
             dd = prep(*dL_dout_depth, "grad_out_depth", dev);
+        }
+        if (dL_dout_alpha && dL_dout_alpha->numel() != 0) {
+            if (dL_dout_alpha->numel() != (long long)H * W)
+                throw std::runtime_error("grad_out_alpha must have H * W elements");
+            da = prep(*dL_dout_alpha, "grad_out_alpha", dev);
         }
         torch::Tensor rad = radii.contiguous();
         if (rad.numel() && (rad.scalar_type() != torch::kInt32 || !rad.is_cuda()))
@@ -174,7 +181,15 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor &background
         char *image = reinterpret_cast<char *>(imageBuffer.data_ptr());
         float *dsh = M ? dL_dsh.data_ptr<float>() : nullptr;
         int st;
-        if (dL_dout_depth)
+        if (dL_dout_alpha)
+            st = gs4d_backward_aux(
+                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
+                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
+                dd.defined() ? fptr(dd) : nullptr, da.defined() ? fptr(da) : nullptr, dL_dmeans2D.data_ptr<float>(),
+                nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
+                dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
+                resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
+        else if (dL_dout_depth)
             st = gs4d_backward_depth(
                 P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
                 fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
@@ -189,7 +204,9 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor &background
                 dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
                 dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(),
                 dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
-        check_status(st, dL_dout_depth ? "rasterize_gaussians_backward_depth" : "rasterize_gaussians_backward");
+        check_status(st, dL_dout_alpha   ? "rasterize_gaussians_backward_aux"
+                         : dL_dout_depth ? "rasterize_gaussians_backward_depth"
+                                         : "rasterize_gaussians_backward");
     }
     return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
                            dL_drotations);
@@ -203,9 +220,9 @@ RasterizeGaussiansBackward(const torch::Tensor &background, const torch::Tensor 
                            const float tan_fovy, const torch::Tensor &dL_dout_color, const torch::Tensor &sh,
                            const int degree, const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
                            const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug) {
-    return BackwardImpl(nullptr, background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-                        viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                        binningBuffer, imageBuffer, debug);
+    return BackwardImpl(nullptr, nullptr, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
+                        geomBuffer, R, binningBuffer, imageBuffer, debug);
 }
 
 // the same with the depth image's gradient (1, H, W) or (H, W) after dL_dout_color: gs4d_backward_depth
@@ -219,9 +236,44 @@ RasterizeGaussiansBackwardDepth(const torch::Tensor &background, const torch::Te
                                 const torch::Tensor &sh, const int degree, const torch::Tensor &campos,
                                 const torch::Tensor &geomBuffer, const int R, const torch::Tensor &binningBuffer,
                                 const torch::Tensor &imageBuffer, const bool debug) {
-    return BackwardImpl(&dL_dout_depth, background, means3D, radii, colors, scales, rotations, scale_modifier,
+    return BackwardImpl(&dL_dout_depth, nullptr, background, means3D, radii, colors, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                         geomBuffer, R, binningBuffer, imageBuffer, debug);
+}
+
+// the same with the alpha image's gradient after the depth image's: gs4d_backward_aux.  An empty tensor for
+// either means "none" (both empty: the colour-only backward's bits)
+BackwardTuple
+RasterizeGaussiansBackwardAux(const torch::Tensor &background, const torch::Tensor &means3D,
+                              const torch::Tensor &radii, const torch::Tensor &colors, const torch::Tensor &scales,
+                              const torch::Tensor &rotations, const float scale_modifier,
+                              const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+                              const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy,
+                              const torch::Tensor &dL_dout_color, const torch::Tensor &dL_dout_depth,
+                              const torch::Tensor &dL_dout_alpha, const torch::Tensor &sh, const int degree,
+                              const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
+                              const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug) {
+    return BackwardImpl(&dL_dout_depth, &dL_dout_alpha, background, means3D, radii, colors, scales, rotations,
+                        scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                        degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug);
+}
+
+// the alpha image 1 - T_final (1, H, W) of the forward that filled imageBuffer: gs4d_alpha_image
+torch::Tensor AlphaImage(const torch::Tensor &imageBuffer, const int image_height, const int image_width) {
+    if (!imageBuffer.is_cuda())
+        throw std::runtime_error("imageBuffer must be a HIP (GPU) tensor; the MI355X rasterizer has no CPU path");
+    if (image_height <= 0 || image_width <= 0) throw std::runtime_error("alpha_image: the image must be non-empty");
+    const long long need = 8LL * image_height * image_width;  // final_T and n_contrib precede the tile tables
+    if (imageBuffer.scalar_type() != torch::kByte || imageBuffer.numel() < need)
+        throw std::runtime_error("alpha_image: imageBuffer is not the image state of an H x W forward");
+    const auto dev = imageBuffer.device();
+    c10::hip::HIPGuard guard(dev.index());
+    torch::Tensor out = torch::empty({1, image_height, image_width}, imageBuffer.options().dtype(torch::kFloat32));
+    hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    check_status(gs4d_alpha_image(image_width, image_height, reinterpret_cast<const char *>(imageBuffer.data_ptr()),
+                                  out.data_ptr<float>(), (void *)stream),
+                 "alpha_image");
+    return out;
 }
 
 // rasterize_points.cu:200-219
@@ -280,6 +332,8 @@ PYBIND11_MODULE(_C, m) {
     m.def("debug_pair_alpha", &DebugPairAlpha);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
     m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);
+    m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux);
+    m.def("alpha_image", &AlphaImage);
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });
     m.def("last_timings", &last_timings);

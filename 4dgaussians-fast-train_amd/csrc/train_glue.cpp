@@ -89,6 +89,50 @@ std::tuple<torch::Tensor, torch::Tensor> l1_loss_grad(const torch::Tensor &x_, c
     return {loss, grad};
 }
 
+// depth + mask supervision of one view (gs4d_aux_loss_grad): returns (loss (0-dim), dL/ddepth, dL/dalpha); an
+// empty gt_depth or gt_mask drops that term, and its gradient comes back empty
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> aux_loss_grad(const torch::Tensor &depth_,
+                                                                      const torch::Tensor &alpha_,
+                                                                      const torch::Tensor &gt_depth_,
+                                                                      const torch::Tensor &gt_mask_, double w_depth,
+                                                                      double w_mask) {
+    const bool has_d = gt_depth_.numel() != 0, has_m = gt_mask_.numel() != 0;
+    need(has_d || has_m, "aux_loss_grad: give gt_depth, gt_mask or both");
+    const torch::Tensor &like = has_d ? depth_ : alpha_;
+    need(like.is_cuda(), "aux_loss_grad: inputs must be HIP (GPU) tensors");
+    c10::hip::HIPGuard guard(like.device().index());
+    const int64_t n = like.numel();
+    need(n >= 1, "aux_loss_grad: empty image");
+    auto prep = [&](const torch::Tensor &t, const char *name) {
+        need(t.is_cuda() && t.device() == like.device(),
+             std::string("aux_loss_grad: ") + name + " must be a HIP (GPU) tensor on the images' device");
+        need(t.numel() == n, std::string("aux_loss_grad: ") + name + " must have the images' number of pixels");
+        return t.detach().to(torch::kFloat32).contiguous();
+    };
+    torch::Tensor depth, alpha, gt_depth, gt_mask, gd, ga;
+    torch::Tensor none = torch::empty({0}, like.options().dtype(torch::kFloat32));
+    gd = ga = none;
+    if (has_d) {
+        depth = prep(depth_, "depth");
+        gt_depth = prep(gt_depth_, "gt_depth");
+        gd = torch::empty(depth_.sizes(), depth.options());
+    }
+    if (has_m) {
+        alpha = prep(alpha_, "alpha");
+        gt_mask = prep(gt_mask_, "gt_mask");
+        ga = torch::empty(alpha_.sizes(), alpha.options());
+    }
+    torch::Tensor loss = torch::empty({}, none.options());
+    torch::Tensor scratch = torch::empty({(int64_t)gs4d_aux_loss_scratch_bytes(n)}, none.options().dtype(torch::kUInt8));
+    check(gs4d_aux_loss_grad(n, has_d ? depth.data_ptr<float>() : nullptr, has_m ? alpha.data_ptr<float>() : nullptr,
+                             has_d ? gt_depth.data_ptr<float>() : nullptr, has_m ? gt_mask.data_ptr<float>() : nullptr,
+                             (float)w_depth, (float)w_mask, loss.data_ptr<float>(),
+                             has_d ? gd.data_ptr<float>() : nullptr, has_m ? ga.data_ptr<float>() : nullptr,
+                             scratch.data_ptr(), stream_of(like)),
+          "aux_loss_grad");
+    return {loss, gd, ga};
+}
+
 torch::Tensor l1_backward(const torch::Tensor &sign, const torch::Tensor &dloss_) {
     c10::hip::HIPGuard guard(sign.device().index());
     torch::Tensor dloss = dloss_.to(torch::kFloat32).contiguous();
@@ -1326,6 +1370,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("l1_forward", &l1_forward);
     m.def("l1_backward", &l1_backward);
     m.def("l1_loss_grad", &l1_loss_grad);
+    m.def("aux_loss_grad", &aux_loss_grad);
     m.def("ssim_forward", &ssim_forward);
     m.def("ssim_backward", &ssim_backward);
     m.def("l1_dssim_loss_grad", &l1_dssim_loss_grad);

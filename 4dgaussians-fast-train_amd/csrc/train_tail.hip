@@ -125,6 +125,108 @@ __global__ __launch_bounds__(kTailThreads) void l1_backward_v4_kernel(int64_t n4
     }
 }
 
+// ---- depth + mask supervision (gs4d_aux_loss_grad) ----------------------------------------------
+// w_depth * mean over the valid pixels (gt_depth > 0) of |depth - gt_depth| + w_mask * mean |alpha - gt_mask|,
+// with both gradient images, in two launches and without a host readback of the valid count:
+//   1. every workgroup stores its three partials (S |depth - gt|, the valid count, S |alpha - mask|) at its own
+//      slot of the scratch (no atomics, nothing to zero);
+//   2. every workgroup totals all the slots in the same fixed order (a few KB from L2: one slot per 2048
+//      pixels), so each holds the same n_valid bit for bit, then writes its chunk of the gradient images;
+//      workgroup 0 also writes the value.
+// A NULL gt_depth or gt_mask drops that term: its inputs are not read and its gradient image is not written.
+__device__ __forceinline__ void block_sum3(double &a, double &b, double &c) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_xor(a, off);
+        b += __shfl_xor(b, off);
+        c += __shfl_xor(c, off);
+    }
+    __shared__ double s_w[kTailThreads / 64][3];
+    if ((threadIdx.x & 63) == 0) {
+        s_w[threadIdx.x >> 6][0] = a;
+        s_w[threadIdx.x >> 6][1] = b;
+        s_w[threadIdx.x >> 6][2] = c;
+    }
+    __syncthreads();
+    a = b = c = 0.0;
+#pragma unroll
+    for (int w = 0; w < kTailThreads / 64; w++) {
+        a += s_w[w][0];
+        b += s_w[w][1];
+        c += s_w[w][2];
+    }
+}
+
+__global__ __launch_bounds__(kTailThreads) void aux_partial_kernel(int64_t n, const float *__restrict__ depth,
+                                                                   const float *__restrict__ alpha,
+                                                                   const float *__restrict__ gt_depth,
+                                                                   const float *__restrict__ gt_mask,
+                                                                   double *__restrict__ part) {
+    const int64_t base = (int64_t)blockIdx.x * kL1Chunk;
+    float sd = 0.f, sm = 0.f;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < kL1PerThread; k++) {
+        const int64_t i = base + (int64_t)k * kTailThreads + threadIdx.x;
+        if (i < n) {
+            if (gt_depth) {
+                const float g = gt_depth[i];
+                if (g > 0.f) {
+                    sd += fabsf(depth[i] - g);
+                    cnt++;
+                }
+            }
+            if (gt_mask) sm += fabsf(alpha[i] - gt_mask[i]);
+        }
+    }
+    double a = sd, b = (double)cnt, c = sm;
+    block_sum3(a, b, c);
+    if (threadIdx.x == 0) {
+        part[3 * (size_t)blockIdx.x + 0] = a;
+        part[3 * (size_t)blockIdx.x + 1] = b;
+        part[3 * (size_t)blockIdx.x + 2] = c;
+    }
+}
+
+__global__ __launch_bounds__(kTailThreads) void aux_grad_kernel(int64_t n, const float *__restrict__ depth,
+                                                                const float *__restrict__ alpha,
+                                                                const float *__restrict__ gt_depth,
+                                                                const float *__restrict__ gt_mask, float w_depth,
+                                                                float w_mask, const double *__restrict__ part,
+                                                                float *__restrict__ loss, float *__restrict__ dL_ddepth,
+                                                                float *__restrict__ dL_dalpha) {
+    // the totals, by every workgroup alike: thread t takes the slots t, t + 256, ... in ascending order
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (int i = (int)threadIdx.x; i < (int)gridDim.x; i += kTailThreads) {
+        a += part[3 * (size_t)i + 0];
+        b += part[3 * (size_t)i + 1];
+        c += part[3 * (size_t)i + 2];
+    }
+    block_sum3(a, b, c);
+    const double n_valid = b < 1.0 ? 1.0 : b;  // max(1, count)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *loss = (float)((double)w_depth * a / n_valid + (double)w_mask * c / (double)n);
+    const float scale_d = (float)((double)w_depth / n_valid);
+    const float scale_m = (float)((double)w_mask / (double)n);
+    const int64_t base = (int64_t)blockIdx.x * kL1Chunk;
+#pragma unroll
+    for (int k = 0; k < kL1PerThread; k++) {
+        const int64_t i = base + (int64_t)k * kTailThreads + threadIdx.x;
+        if (i < n) {
+            if (gt_depth) {
+                const float g = gt_depth[i];
+                const float d = depth[i] - g;
+                const float sg = (float)((d > 0.f) - (d < 0.f));  // torch.sign: 0 at 0
+                dL_ddepth[i] = g > 0.f ? sg * scale_d : 0.f;
+            }
+            if (gt_mask) {
+                const float d = alpha[i] - gt_mask[i];
+                dL_dalpha[i] = (float)((d > 0.f) - (d < 0.f)) * scale_m;
+            }
+        }
+    }
+}
+
 // ---- densification statistics ------------------------------------------------------------------
 __global__ __launch_bounds__(kTailThreads) void densify_stats_kernel(int P, const float *__restrict__ vs_grad,
                                                                      const uint8_t *__restrict__ visible,
@@ -693,6 +795,28 @@ int gs4d_l1_loss_grad(int64_t n, const float *x, const float *y, float dloss, fl
     hipLaunchKernelGGL(l1_partial_v4_kernel<true>, dim3((unsigned)nblk), dim3(kTailThreads), 0, s, n / 4,
                        (const float4 *)x, (const float4 *)y, (char4 *)nullptr, ticket_scratch(scratch), loss,
                        (float4 *)grad, scale);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+size_t gs4d_aux_loss_scratch_bytes(int64_t n) {
+    return n > 0 ? 24 * (size_t)((n + kL1Chunk - 1) / kL1Chunk) + 256 : 256;
+}
+
+int gs4d_aux_loss_grad(int64_t n, const float *depth, const float *alpha, const float *gt_depth, const float *gt_mask,
+                       float w_depth, float w_mask, float *loss, float *dL_ddepth, float *dL_dalpha, void *scratch,
+                       void *stream) {
+    if (n < 1 || !loss || !scratch) return 1;
+    if (gt_depth && (!depth || !dL_ddepth)) return 1;
+    if (gt_mask && (!alpha || !dL_dalpha)) return 1;
+    const int64_t nblk = (n + kL1Chunk - 1) / kL1Chunk;
+    if (nblk > INT32_MAX) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)(((size_t)scratch + 7) & ~(size_t)7);
+    hipLaunchKernelGGL(aux_partial_kernel, dim3((unsigned)nblk), dim3(kTailThreads), 0, s, n, depth, alpha, gt_depth,
+                       gt_mask, part);
+    if (hipGetLastError() != hipSuccess) return 3;
+    hipLaunchKernelGGL(aux_grad_kernel, dim3((unsigned)nblk), dim3(kTailThreads), 0, s, n, depth, alpha, gt_depth,
+                       gt_mask, w_depth, w_mask, (const double *)part, loss, dL_ddepth, dL_dalpha);
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 

@@ -8,9 +8,11 @@ Public surface identical to the reference package
   rasterize_gaussians            functional entry (:21-42)
   _RasterizeGaussians            torch.autograd.Function (:44-155)
 
-so gaussian_renderer/__init__.py and train.py run unchanged.  One opt-in extension, off by default:
+so gaussian_renderer/__init__.py and train.py run unchanged.  Two opt-in extensions, off by default:
 depth_grad=True (rasterize_gaussians, GaussianRasterizer) selects _RasterizeGaussiansDepth, whose backward
-also back-propagates the depth image's gradient, which the reference drops (:100-101).  The compute runs in libgs4d (HIP
+also back-propagates the depth image's gradient, which the reference drops (:100-101); alpha=True selects
+_RasterizeGaussiansAux, which also returns the accumulated-alpha image 1 - T_final (1, H, W) as a fourth,
+differentiable output (the reference returns no such image, :98).  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
 without the built extension raises ImportError -- there is no CPU fallback.
 """
@@ -22,7 +24,7 @@ import torch.nn as nn
 from . import _C  # noqa: F401  (fails loudly when the HIP extension is missing)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansDepth"]
+           "_RasterizeGaussiansDepth", "_RasterizeGaussiansAux", "_RasterizeGaussiansAuxDepth"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -59,8 +61,12 @@ def _invoke(fn, args, debug, dump_name, stage):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_grad=False):
-    fn = _RasterizeGaussiansDepth if depth_grad else _RasterizeGaussians
+                        raster_settings, depth_grad=False, alpha=False):
+    """(color, radii, depth), or with alpha=True (color, radii, depth, alpha)"""
+    if alpha:
+        fn = _RasterizeGaussiansAuxDepth if depth_grad else _RasterizeGaussiansAux
+    else:
+        fn = _RasterizeGaussiansDepth if depth_grad else _RasterizeGaussians
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                     raster_settings)
 
@@ -130,16 +136,76 @@ class _RasterizeGaussiansDepth(torch.autograd.Function):
         return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
 
 
+class _RasterizeGaussiansAux(torch.autograd.Function):
+    """_RasterizeGaussians that also returns the alpha image 1 - T_final (opt-in: alpha=True), whose gradient flows
+    back through _C.rasterize_gaussians_backward_aux; the depth image's gradient is dropped, as by default."""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        return _aux_forward(ctx, False, *inputs)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha):
+        return _aux_backward(ctx, grad_out_color, grad_depth, grad_alpha)
+
+
+class _RasterizeGaussiansAuxDepth(torch.autograd.Function):
+    """_RasterizeGaussiansAux whose backward takes the depth image's gradient too (alpha=True, depth_grad=True)."""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        return _aux_forward(ctx, True, *inputs)
+
+    backward = staticmethod(_RasterizeGaussiansAux.backward)
+
+
+def _aux_forward(ctx, depth_grad, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                 raster_settings):
+    # the same _C.rasterize_gaussians call and saved tensors as _RasterizeGaussians.forward, then the alpha image
+    color, radii, depth = _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
+                                                      rotations, cov3Ds_precomp, raster_settings)
+    ctx.depth_grad = depth_grad
+    s = raster_settings
+    img_buf = ctx.to_save[-1]  # the forward's image state (save_for_backward's last tensor)
+    if means3D.shape[0] == 0:  # nothing was drawn and there is no image state to read
+        alpha = torch.zeros((1, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
+    else:
+        alpha = _C.alpha_image(img_buf, s.image_height, s.image_width)
+    return color, radii, depth, alpha
+
+
+def _aux_backward(ctx, grad_out_color, grad_depth, grad_alpha):
+    s = ctx.raster_settings
+    if not ctx.depth_grad:
+        grad_depth = None
+    if grad_out_color is None and grad_depth is None and grad_alpha is None:
+        return (None,) * 9
+    (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
+     img_buf) = ctx.saved_tensors
+    if grad_out_color is None:
+        grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
+    none = torch.empty(0, dtype=torch.float32, device=means3D.device)  # "no such gradient"
+    # _C.rasterize_gaussians_backward_depth's positional order with grad_alpha after grad_depth
+    args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color,
+            none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha, sh, s.sh_degree,
+            s.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
+    (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _invoke(
+        _C.rasterize_gaussians_backward_aux, args, s.debug, "snapshot_bw.dump", "backward")
+    return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+
+
 def _empty_if_none(t):
     # "not provided" travels as an empty tensor (reference :197-207)
     return torch.Tensor([]) if t is None else t
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings, depth_grad=False):
+    def __init__(self, raster_settings, depth_grad=False, alpha=False):
         super().__init__()
         self.raster_settings = raster_settings
         self.depth_grad = depth_grad  # opt-in: the depth image's gradient flows back (_RasterizeGaussiansDepth)
+        self.alpha = alpha  # opt-in: forward also returns the alpha image 1 - T_final (_RasterizeGaussiansAux)
 
     def markVisible(self, positions):
         """Near-plane visibility mask of `positions` for this camera (reference :176-185)."""
@@ -157,4 +223,4 @@ class GaussianRasterizer(nn.Module):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, _empty_if_none(shs), _empty_if_none(colors_precomp), opacities,
                                    _empty_if_none(scales), _empty_if_none(rotations), _empty_if_none(cov3D_precomp),
-                                   self.raster_settings, depth_grad=self.depth_grad)
+                                   self.raster_settings, depth_grad=self.depth_grad, alpha=self.alpha)

@@ -32,7 +32,8 @@ def optimization_params(**over):
              densify_grad_threshold_after=0.0002, pruning_from_iter=500, pruning_interval=100,
              opacity_threshold_coarse=0.005, opacity_threshold_fine_init=0.005, opacity_threshold_fine_after=0.005,
              batch_size=1, add_point=False,
-             lambda_depth=0.0)  # this build's opt-in: weight of the depth L1 on (camera, gt, gt_depth) views (train.py)
+             lambda_depth=0.0,  # this build's opt-in: weight of the depth L1 on (camera, gt, gt_depth) views (train.py)
+             lambda_mask=0.0)  # opt-in: weight of mean |alpha - gt_mask| on (camera, gt, gt_depth or None, gt_mask) views
     d.update(over)
     return SimpleNamespace(**d)
 

@@ -13,7 +13,7 @@ import torch.optim.optimizer as _optim_mod
 from . import _C
 
 __all__ = ["deform_tail", "l1_loss", "ssim", "l1_dssim_loss_and_grad", "densify_stats", "FusedAdam", "hexplane", "hexplane_points", "set_deterministic", "hexplane_regulation", "hexplane_regulation_value",
-           "hexplane_regulation_accumulate_grad"]
+           "hexplane_regulation_accumulate_grad", "aux_loss_and_grad"]
 
 
 class _L1Loss(torch.autograd.Function):
@@ -46,6 +46,19 @@ def l1_loss_and_grad(network_output, gt, dloss=1.0):
         return _C.l1_loss_grad(x, y, float(dloss))
     loss, sign = _C.l1_forward(x, y)
     return loss, _C.l1_backward(sign, torch.full((1,), float(dloss), device=x.device)).to(x.dtype)
+
+
+def aux_loss_and_grad(depth, alpha, gt_depth, gt_mask, w_depth, w_mask):
+    """Depth + mask supervision of one view in two launches (gs4d_aux_loss_grad): the detached value
+    w_depth * mean over gt_depth > 0 of |depth - gt_depth| + w_mask * mean |alpha - gt_mask| (the valid count, at
+    least 1, never leaves the device) and its gradients (dL/ddepth, dL/dalpha), shaped like depth and alpha.
+    gt_depth or gt_mask may be None: that term is dropped and its gradient is None."""
+    dev = (depth if gt_depth is not None else alpha).device
+    none = torch.empty(0, device=dev)
+    loss, g_d, g_a = _C.aux_loss_grad(none if gt_depth is None else depth, none if gt_mask is None else alpha,
+                                      none if gt_depth is None else gt_depth, none if gt_mask is None else gt_mask,
+                                      float(w_depth), float(w_mask))
+    return loss, (None if gt_depth is None else g_d), (None if gt_mask is None else g_a)
 
 
 class _Ssim(torch.autograd.Function):

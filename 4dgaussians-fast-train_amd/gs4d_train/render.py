@@ -100,9 +100,11 @@ class RenderPackage(dict):
         return dict.__len__(self)
 
 
-def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False):
+def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False,
+           alpha=False):
     """depth_grad=True (this build's opt-in): the gradient of the returned "depth" flows back through the
-    rasterizer; by default it is dropped, as in the reference."""
+    rasterizer; by default it is dropped, as in the reference.  alpha=True (opt-in as well): the package gains
+    "alpha", the accumulated alpha 1 - T_final of every pixel (1, H, W), whose gradient flows back too."""
     xyz = pc.get_xyz
     # the rasterizer's means2D gradient sink (:24-29 builds zeros + 0 and retains its grad; a zero leaf
     # holds the same values and receives the same .grad)
@@ -121,7 +123,7 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
     # torch.tensor(time).to(dev).repeat(P, 1) (:52): the same float32 column, as one device value broadcast
     # over the P rows (made once per (device, time); no fill per call)
     time = _time_value(_time_float(viewpoint_camera.time), dev).expand(xyz.shape[0], 1)
-    rasterizer = dgr.GaussianRasterizer(raster_settings=settings, depth_grad=depth_grad)
+    rasterizer = dgr.GaussianRasterizer(raster_settings=settings, depth_grad=depth_grad, alpha=alpha)
     if "coarse" not in stage and "fine" not in stage:
         raise NotImplementedError(stage)
     if getattr(pc, "fused", False) and getattr(pc, "fused_tail", True) and xyz.is_cuda:
@@ -141,6 +143,10 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
         sc = pc.scaling_activation(sc)
         rot = pc.rotation_activation(rot)
         op = pc.opacity_activation(op)
-    image, radii, depth = rasterizer(means3D=m3, means2D=screenspace_points, shs=sh, colors_precomp=None,
-                                     opacities=op, scales=sc, rotations=rot, cov3D_precomp=None)
+    out = rasterizer(means3D=m3, means2D=screenspace_points, shs=sh, colors_precomp=None,
+                     opacities=op, scales=sc, rotations=rot, cov3D_precomp=None)
+    image, radii, depth = out[:3]
+    if alpha:
+        return RenderPackage(render=image, viewspace_points=screenspace_points, radii=radii, depth=depth,
+                             alpha=out[3])
     return RenderPackage(render=image, viewspace_points=screenspace_points, radii=radii, depth=depth)

@@ -14,6 +14,11 @@ radii and visibility are reduced so every replica takes the single-process step.
 Depth supervision (this build's opt-in, no reference counterpart): with opt.lambda_depth != 0 a view given as
 (camera, gt_image, gt_depth) adds lambda_depth * mean over the valid pixels (gt_depth > 0) of
 |depth - gt_depth| to the loss, and is rendered with depth_grad=True so the term reaches the Gaussians.
+
+Mask supervision (opt-in as well): with opt.lambda_mask != 0 a view given as (camera, gt_image, gt_depth or None,
+gt_mask) is rendered with alpha=True and adds lambda_mask * mean |alpha - gt_mask|, alpha being the rasterizer's
+accumulated-alpha image 1 - T_final.  Such a view's depth and mask terms come from one fused kernel pair on the
+fused path (kernels.aux_loss_and_grad); views without a mask take the code they took before.
 """
 import torch
 
@@ -32,11 +37,14 @@ def depth_l1(depth, gt_depth):
 
 def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine", fused_loss=None,
                data_parallel=False, render_fn=None):
-    """views: list of (camera, gt_image (3, H, W)) or (camera, gt_image, gt_depth (1, H, W) or (H, W)); the
-    depth is read only when opt.lambda_depth != 0.  Returns the (detached) batch loss tensor.
+    """views: list of (camera, gt_image (3, H, W)), (camera, gt_image, gt_depth (1, H, W) or (H, W)) or
+    (camera, gt_image, gt_depth or None, gt_mask (1, H, W) or (H, W), floats in [0, 1]); the depth is read only
+    when opt.lambda_depth != 0 and the mask only when opt.lambda_mask != 0.  Returns the (detached) batch loss
+    tensor.
 
     render_fn(camera, gaussians, debug, bg, stage=...) -> render()'s dict; defaults to
-    gs4d_train.render.render (the HIP rasterizer).  The multi-process CPU tests pass a torch stand-in."""
+    gs4d_train.render.render (the HIP rasterizer).  The multi-process CPU tests pass a torch stand-in.  It is
+    called with depth_grad=True and / or alpha=True only for the views that need them."""
     if render_fn is None:
         from .render import render as render_fn
     fused = gaussians.fused if fused_loss is None else fused_loss
@@ -46,10 +54,20 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     mine = dp.shard_views(len(views)) if data_parallel else list(range(len(views)))
     images, gts, radii_list, vis_list, vs_list = [], [], [], [], []
     lambda_depth = getattr(opt, "lambda_depth", 0.0)
+    lambda_mask = getattr(opt, "lambda_mask", 0.0)
     depths, gt_depths = [], []  # of the views that carry a gt depth, when lambda_depth != 0
+    masked = []  # (depth or None, gt_depth or None, alpha, gt_mask) of the views that carry a mask, when lambda_mask != 0
     for v in mine:
         cam, gt = views[v][0], views[v][1]
-        if lambda_depth != 0 and len(views[v]) > 2:
+        has_depth = lambda_depth != 0 and len(views[v]) > 2 and views[v][2] is not None
+        if lambda_mask != 0 and len(views[v]) > 3 and views[v][3] is not None:
+            if has_depth:
+                pkg = render_fn(cam, gaussians, False, background, stage=stage, depth_grad=True, alpha=True)
+                masked.append((pkg["depth"], views[v][2], pkg["alpha"], views[v][3]))
+            else:
+                pkg = render_fn(cam, gaussians, False, background, stage=stage, alpha=True)
+                masked.append((None, None, pkg["alpha"], views[v][3]))
+        elif has_depth:
             pkg = render_fn(cam, gaussians, False, background, stage=stage, depth_grad=True)
             depths.append(pkg["depth"])
             gt_depths.append(views[v][2])
@@ -117,6 +135,28 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
             for d, gd in zip(depths, gt_depths):
                 total, _, n = depth_l1(d, gd)
                 loss = loss + total / n * scale
+    aux_tensors, aux_grads = [], []
+    if masked:
+        # per view: lambda_depth * valid-pixel mean |depth - gt_depth| + lambda_mask * mean |alpha - gt_mask|, scaled
+        # like the depth term above
+        scale = share / len(mine)
+        for d, gd, a, gm in masked:
+            if image_grad is not None:
+                # fused path: the view's value and both gradient images in two launches (gs4d_aux_loss_grad)
+                from .kernels import aux_loss_and_grad
+                value, g_d, g_a = aux_loss_and_grad(d, a, None if gd is None else gd.reshape(d.shape),
+                                                    gm.reshape(a.shape), lambda_depth * scale, lambda_mask * scale)
+                loss = loss + value
+                if d is not None:
+                    aux_tensors.append(d)
+                    aux_grads.append(g_d)
+                aux_tensors.append(a)
+                aux_grads.append(g_a)
+            else:
+                if d is not None:
+                    total, _, n = depth_l1(d, gd)
+                    loss = loss + total / n * (lambda_depth * scale)
+                loss = loss + (a - gm.reshape(a.shape)).abs().mean() * (lambda_mask * scale)
     reg_w = (hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight)
     reg_scale = 1.0 / dp.world() if data_parallel else 1.0
     reg_deferred = False
@@ -135,7 +175,11 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     # a data-parallel rank with no view of the batch (len(views) < world) and no regulariser has a
     # constant loss: nothing to back-propagate, its gradients are the zeros filled in below
     if image_grad is not None:
-        if image_tensor.requires_grad and depth_grads:
+        if image_tensor.requires_grad and aux_tensors:
+            # one backward pass: each view's rasterizer backward takes its colour, depth and alpha gradients together
+            torch.autograd.backward([image_tensor] + depths + aux_tensors,
+                                    [image_grad] + (depth_grads or []) + aux_grads)
+        elif image_tensor.requires_grad and depth_grads:
             # one backward pass: each view's rasterizer backward takes its colour and depth gradients together
             torch.autograd.backward([image_tensor] + depths, [image_grad] + depth_grads)
         elif image_tensor.requires_grad:

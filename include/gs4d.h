@@ -122,6 +122,36 @@ int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int
                         float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug,
                         void *stream, int view_transposed);
 
+/* The alpha image of a forward (no reference counterpart; opt-in): out_alpha[pix] = 1 - final_T[pix] =
+ * sum alpha_i T_i, the accumulated alpha of the pixel, read from the image state a gs4d_forward left in
+ * image_buffer.  The reference stores final_T per pixel for its backward (forward.cu:373) and returns no such
+ * image: its rasterizer hands out colour, radii and depth only (diff_gaussian_rasterization/__init__.py:98).
+ * It is what normalises the depth image (forward.cu:359 has no background term), what a foreground mask is
+ * compared with, and what compositing over another background needs.  Pixels of tiles with an empty list, and
+ * every pixel when num_rendered == 0, give 0.  out_alpha: width * height floats on the device.  One streaming
+ * launch on `stream`.
+ * Status: GS4D_ERR_ARG for width <= 0, height <= 0 or a NULL pointer. */
+int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out_alpha, void *stream);
+
+/* gs4d_backward_depth with a gradient for the alpha image of gs4d_alpha_image as well (no reference
+ * counterpart; opt-in).  dL_ddepth and dL_dalpha (H * W floats each) may each be NULL: "no such gradient".
+ * Both NULL is gs4d_backward_ex, dL_dalpha == NULL is gs4d_backward_depth, bit for bit; with dL_ddepth == NULL
+ * the colour-only instantiations of the three stages run.  Since d(1 - T_final)/dalpha_i = T_final / (1 - alpha_i),
+ * the factor the reference's background term already carries (backward.cu:531-534), dL_dalpha enters as the
+ * start value of the reverse walk's running sum, bg . dL_dpix - dL_dalpha, and nowhere else: it reaches
+ * dL_dopacity, dL_dmean2D and dL_dconic (hence dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot); dL_dcolor and
+ * dL_dsh receive nothing from it.  Results are bitwise repeatable.
+ * Status as gs4d_backward_depth: GS4D_OK at once for P == 0; GS4D_ERR_ARG for P < 0, R < 0 or a NULL dL_dpix. */
+int gs4d_backward_aux(int P, int D, int M, int R, const float *background, int width, int height,
+                      const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                      float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                      const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                      float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                      const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
+                      float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                      float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
+                      int debug, void *stream, int view_transposed);
+
 /* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.

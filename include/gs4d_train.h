@@ -32,6 +32,23 @@ int gs4d_l1_loss_grad(int64_t n, const float *x, const float *y, float dloss, fl
                       void *stream);
 int gs4d_l1_loss_backward(int64_t n, const int8_t *sign, const float *dloss, float *grad, void *stream);
 
+/* ---- depth + mask supervision of one view (this build's opt-in; no reference counterpart: the reference's
+ * Camera carries `depth` and `mask`, scene/cameras.py:21,54, and no loss reads them).  Over the n pixels of the
+ * depth image and the alpha image (gs4d_alpha_image), with valid = gt_depth > 0 and n_valid = max(1, count(valid))
+ * counted on the device (no host readback):
+ *   *loss        = w_depth * (sum over valid of |depth - gt_depth|) / n_valid + w_mask * (sum |alpha - gt_mask|) / n
+ *   dL_ddepth[i] = w_depth * sign(depth[i] - gt_depth[i]) / n_valid where valid, 0 elsewhere
+ *   dL_dalpha[i] = w_mask * sign(alpha[i] - gt_mask[i]) / n                          (sign(0) = 0)
+ * A NULL gt_depth or gt_mask drops that term; its inputs are then not read, its gradient image is not written
+ * and both may be NULL.  Any n >= 1.  Two launches; the sums run in a fixed order (fp64 partials per 2048
+ * pixels, totalled alike by every workgroup), so the value and both images are bitwise repeatable.  scratch:
+ * gs4d_aux_loss_scratch_bytes(n) bytes, contents irrelevant on entry (one scratch per stream).
+ * Status: 1 for n < 1, a NULL loss or scratch, or a NULL image of a term that is present. */
+size_t gs4d_aux_loss_scratch_bytes(int64_t n);
+int gs4d_aux_loss_grad(int64_t n, const float *depth, const float *alpha, const float *gt_depth, const float *gt_mask,
+                       float w_depth, float w_mask, float *loss, float *dL_ddepth, float *dL_dalpha, void *scratch,
+                       void *stream);
+
 /* ---- SSIM / D-SSIM: utils/loss_utils.py:36-66 ssim(img1, img2, window_size=11, size_average): the 11x11
  * Gaussian window (sigma 1.5, normalised), zero padding of 5, one filter per channel, C1 = 0.01^2,
  * C2 = 0.03^2, map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), applied separably

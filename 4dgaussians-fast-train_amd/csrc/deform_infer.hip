@@ -267,11 +267,13 @@ static size_t di_lds_bytes(int F, int W, int npad) {
 }
 
 // dynamic LDS above 64 KiB (gfx950: 160 KiB per workgroup): raised once per (device, kernel); false when the device
-// cannot give it
+// cannot give it.  slot: the kernel's index among the kDiKernels instantiations gs4d_deform_infer launches
+constexpr int kDiKernels = 4;
 static bool di_raise_lds(const void *kern, int slot, size_t need) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    static int state[3][64] = {};  // 0 unknown, 1 raised, 2 unavailable
+    static int state[kDiKernels][64] = {};  // 0 unknown, 1 raised, 2 unavailable
+    if (slot < 0 || slot >= kDiKernels) return false;
     int &st = state[slot][dev];
     if (st == 0) {
         int maxlds = 0;
@@ -294,10 +296,11 @@ int gs4d_deform_infer(const gs4d_deform_infer_args *args, void *stream) {
     if (!args) return bad("null arguments");
     const gs4d_deform_infer_args &b = *args;
     if (b.P < 0) return bad("P < 0");
-    const bool shape_ok = (b.F == 32 && b.W == 128) || (b.F == 64 && b.W == 64) || (b.F == 32 && b.W == 64);
+    const bool shape_ok = (b.F == 32 && b.W == 128) || (b.F == 48 && b.W == 128) || (b.F == 64 && b.W == 64) ||
+                          (b.F == 32 && b.W == 64);
     if (!shape_ok)
         return bad("(F, W) = (" + std::to_string(b.F) + ", " + std::to_string(b.W) +
-                   ") is not one of (32, 128), (64, 64), (32, 64)");
+                   ") is not one of (32, 128), (48, 128), (64, 64), (32, 64)");
     if (b.k < 1 || b.k > kDiRoles) return bad("k = " + std::to_string(b.k) + " heads (1..5)");
     if (b.K < 1) return bad("K < 1");
     static const int role_n[kDiRoles] = {3, 3, 4, 1, 48};
@@ -350,7 +353,8 @@ int gs4d_deform_infer(const gs4d_deform_infer_args *args, void *stream) {
     };
     if (b.F == 32 && b.W == 128) return go(deform_infer_kernel<32, 128>, 0);
     if (b.F == 64 && b.W == 64) return go(deform_infer_kernel<64, 64>, 1);
-    return go(deform_infer_kernel<32, 64>, 2);
+    if (b.F == 32 && b.W == 64) return go(deform_infer_kernel<32, 64>, 2);
+    return go(deform_infer_kernel<48, 128>, 3);
 }
 
 }  // extern "C"

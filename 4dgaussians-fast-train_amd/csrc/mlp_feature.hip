@@ -21,8 +21,17 @@ namespace gs4d {
 // partials in workgroup order (deterministic).
 constexpr int kFbThreads = 256, kFbRows = 16;
 
-template <int FIN, int FOUT>
-__global__ __launch_bounds__(kFbThreads) void feature_bwd_kernel(int P, const float *__restrict__ g,
+// LATEX (the (48, 128) instantiation): the next block's x loads are issued after this block's dW MFMAs instead of
+// before its dx MFMAs, so x needs one register set (xb) and no copy (xc), and the kernel is held to two waves per
+// SIMD (252 registers where the plain body takes 168 + 108 and one wave).  The MFMA chains, and so every bit of the
+// results, are the same; measured 50.6 us against the plain body's 63.1 at P = 100k.
+// -DGS4D_FB48_LATE_X=0 builds the plain body for that shape, to measure the two against each other again.
+#ifndef GS4D_FB48_LATE_X
+#define GS4D_FB48_LATE_X 1
+#endif
+constexpr bool kFb48LateX = GS4D_FB48_LATE_X != 0;
+template <int FIN, int FOUT, bool LATEX = false>
+__global__ __launch_bounds__(kFbThreads, LATEX ? 2 : 1) void feature_bwd_kernel(int P, const float *__restrict__ g,
                                                                  const float *__restrict__ h,
                                                                  const float *__restrict__ x,
                                                                  const float *__restrict__ w, float *__restrict__ dx,
@@ -56,6 +65,15 @@ __global__ __launch_bounds__(kFbThreads) void feature_bwd_kernel(int P, const fl
     // rows past P (and the prefetch past the last block) read row P - 1, masked when the block comes up:
     // unconditional loads let the compiler's waits count exactly the loads issued after a block's (with a
     // branch around them it waited for every load in flight, the next block's prefetch included)
+    auto load_x = [&](int blk) {
+        const int r0 = blk * kFbRows;
+#pragma unroll
+        for (int st = 0; st < 4; st++) {
+            const int r = min(r0 + 4 * st + (lane >> 4), P - 1);
+#pragma unroll
+            for (int n = 0; n < NB; n++) xb[st][n] = x[(size_t)r * FIN + 16 * n + (lane & 15)];
+        }
+    };
     auto load_block = [&](int blk) {
         const int r0 = blk * kFbRows;
 #pragma unroll
@@ -64,16 +82,12 @@ __global__ __launch_bounds__(kFbThreads) void feature_bwd_kernel(int P, const fl
             gv[it] = *reinterpret_cast<const float2 *>(g + (size_t)r * FOUT + o);
             hv[it] = *reinterpret_cast<const float2 *>(h + (size_t)r * FOUT + o);
         }
-#pragma unroll
-        for (int st = 0; st < 4; st++) {
-            const int r = min(r0 + 4 * st + (lane >> 4), P - 1);
-#pragma unroll
-            for (int n = 0; n < NB; n++) xb[st][n] = x[(size_t)r * FIN + 16 * n + (lane & 15)];
-        }
+        if constexpr (!LATEX) load_x(blk);
     };
     const int stride = gridDim.x * NW;
     int blk = blockIdx.x * NW + wv;
     load_block(blk);
+    if constexpr (LATEX) load_x(blk);
     for (; blk < nblk; blk += stride) {
         const int r0 = blk * kFbRows;
         // dz = g * (h > 0) into the tile, column sums into db
@@ -87,12 +101,14 @@ __global__ __launch_bounds__(kFbThreads) void feature_bwd_kernel(int P, const fl
             t[row * TS + o] = d0;
             t[row * TS + o + 1] = d1;
         }
-        float xc[4][NB];
+        float xc[LATEX ? 1 : 4][NB];
+        if constexpr (!LATEX) {
 #pragma unroll
-        for (int st = 0; st < 4; st++) {
-            const bool ok = r0 + 4 * st + (lane >> 4) < P;
+            for (int st = 0; st < 4; st++) {
+                const bool ok = r0 + 4 * st + (lane >> 4) < P;
 #pragma unroll
-            for (int n = 0; n < NB; n++) xc[st][n] = ok ? xb[st][n] : 0.f;
+                for (int n = 0; n < NB; n++) xc[st][n] = ok ? xb[st][n] : 0.f;
+            }
         }
         load_block(blk + stride);  // the next block's loads fly while this one runs on the MFMA
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the tile is written (LDS is in order per wave)
@@ -121,14 +137,20 @@ __global__ __launch_bounds__(kFbThreads) void feature_bwd_kernel(int P, const fl
         // dW += dz^T x: A[m = o 16 mb + (l & 15)][k = row 4s + (l >> 4)], B = xb
 #pragma unroll
         for (int st = 0; st < 4; st++) {
+            if constexpr (LATEX) {  // the rows past P masked as they are used
+                const bool ok = r0 + 4 * st + (lane >> 4) < P;
+#pragma unroll
+                for (int n = 0; n < NB; n++) xc[0][n] = ok ? xb[st][n] : 0.f;
+            }
 #pragma unroll
             for (int m = 0; m < MB; m++) {
                 const float av = t[(4 * st + (lane >> 4)) * TS + 16 * m + (lane & 15)];
 #pragma unroll
                 for (int n = 0; n < NB; n++)
-                    accw[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xc[st][n], accw[m][n], 0, 0, 0);
+                    accw[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xc[LATEX ? 0 : st][n], accw[m][n], 0, 0, 0);
             }
         }
+        if constexpr (LATEX) load_x(blk + stride);
         __builtin_amdgcn_wave_barrier();  // the tile's reads are done before the next block overwrites it
     }
     // the waves' partials added in wave order in LDS (W is no longer needed there)
@@ -265,6 +287,11 @@ using namespace gs4d;
 
 extern "C" {
 
+// the (Fin, Fout) the two kernels are instantiated for: DyNeRF / multipleview, HyperNeRF / DyCheck, D-NeRF, small
+static bool fb_shape_ok(int Fin, int Fout) {
+    return (Fin == 32 && Fout == 128) || (Fin == 48 && Fout == 128) || (Fin == 64 && Fout == 64) ||
+           (Fin == 32 && Fout == 64);
+}
 static int fb_grid(int P) {
     const int nblk = (P + kFbRows - 1) / kFbRows;
     return std::max(1, std::min(512, (nblk + 3) / 4));
@@ -276,7 +303,7 @@ size_t gs4d_feature_relu_backward_scratch_bytes(int P, int Fin, int Fout) {
 int gs4d_feature_relu_backward(int P, int Fin, int Fout, const float *g, const float *h, const float *x,
                                const float *w, float *dx, float *dw, float *db, void *scratch, void *stream) {
     if (P < 0 || !w || !dw || !db || !scratch) return 1;
-    if (!((Fin == 32 && Fout == 128) || (Fin == 64 && Fout == 64) || (Fin == 32 && Fout == 64))) return 1;
+    if (!fb_shape_ok(Fin, Fout)) return 1;
     if (P > 0 && (!g || !h || !x || !dx)) return 1;
     if ((((size_t)g | (size_t)h | (size_t)w) & 15) != 0) return 1;
     hipStream_t s = (hipStream_t)stream;
@@ -286,6 +313,9 @@ int gs4d_feature_relu_backward(int P, int Fin, int Fout, const float *g, const f
         if (hipMemsetAsync(part, 0, 4 * (size_t)per, s) != hipSuccess) return 3;
     } else if (Fin == 32 && Fout == 128) {
         hipLaunchKernelGGL((feature_bwd_kernel<32, 128>), dim3(nwg), dim3(kFbThreads), 0, s, P, g, h, x, w, dx, part);
+    } else if (Fin == 48) {
+        hipLaunchKernelGGL((feature_bwd_kernel<48, 128, kFb48LateX>), dim3(nwg), dim3(kFbThreads), 0, s, P, g, h, x, w, dx,
+                           part);
     } else if (Fin == 64) {
         hipLaunchKernelGGL((feature_bwd_kernel<64, 64>), dim3(nwg), dim3(kFbThreads), 0, s, P, g, h, x, w, dx, part);
     } else {
@@ -299,7 +329,7 @@ int gs4d_feature_relu_backward(int P, int Fin, int Fout, const float *g, const f
 int gs4d_feature_relu_forward_hb(int P, int Fin, int Fout, const float *x, const float *w, const float *b, float *h,
                                  uint16_t *hb, void *stream) {
     if (P < 0 || !w || !b) return 1;
-    if (!((Fin == 32 && Fout == 128) || (Fin == 64 && Fout == 64) || (Fin == 32 && Fout == 64))) return 1;
+    if (!fb_shape_ok(Fin, Fout)) return 1;
     if (P == 0) return 0;
     if (!x || !h || (((size_t)x | (size_t)w) & 15) != 0) return 1;
     hipStream_t s = (hipStream_t)stream;
@@ -307,6 +337,8 @@ int gs4d_feature_relu_forward_hb(int P, int Fin, int Fout, const float *x, const
     __bf16 *hbb = reinterpret_cast<__bf16 *>(hb);
     if (Fin == 32 && Fout == 128)
         hipLaunchKernelGGL((feature_fwd_kernel<32, 128>), dim3(nwg), dim3(kFbThreads), 0, s, P, x, w, b, h, hbb);
+    else if (Fin == 48)
+        hipLaunchKernelGGL((feature_fwd_kernel<48, 128>), dim3(nwg), dim3(kFbThreads), 0, s, P, x, w, b, h, hbb);
     else if (Fin == 64)
         hipLaunchKernelGGL((feature_fwd_kernel<64, 64>), dim3(nwg), dim3(kFbThreads), 0, s, P, x, w, b, h, hbb);
     else

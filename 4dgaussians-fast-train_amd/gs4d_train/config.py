@@ -3,7 +3,8 @@
 `model_hidden_params()` / `optimization_params()` return the reference defaults
 (arguments/__init__.py:77-107 and :109-156); the per-dataset files of arguments/ override a few of
 them, e.g. `DYNERF` mirrors arguments/dynerf/default.py (the BASELINE.json metric's camera size)
-and `DNERF` arguments/dnerf/dnerf_default.py.
+and `DNERF` arguments/dnerf/dnerf_default.py; `HYPERNERF` and `DYCHECK` mirror arguments/hypernerf/default.py and
+arguments/dycheck/default.py.
 """
 from types import SimpleNamespace
 
@@ -53,6 +54,21 @@ DNERF_HIDDEN = dict(multires=[1, 2], defor_depth=0, net_width=64, plane_tv_weigh
 DNERF_OPT = dict(coarse_iterations=3000, deformation_lr_init=0.00016, deformation_lr_final=0.0000016,
                  deformation_lr_delay_mult=0.01, grid_lr_init=0.0016, grid_lr_final=0.000016, iterations=20000,
                  pruning_interval=8000, percent_dense=0.01)
+# arguments/hypernerf/default.py (the per-scene files of arguments/hypernerf/ keep these) and
+# arguments/dycheck/default.py: three grid levels, so the field's feature width is 3 * 16 = 48.  render_process
+# (debug image dumps) is left out.
+HYPERNERF_HIDDEN = dict(kplanes_config={"grid_dimensions": 2, "input_coordinate_dim": 4, "output_coordinate_dim": 16,
+                                        "resolution": [64, 64, 64, 150]},
+                        multires=[1, 2, 4], defor_depth=1, net_width=128, plane_tv_weight=0.0002,
+                        time_smoothness_weight=0.001, l1_time_planes=0.0001)
+HYPERNERF_OPT = dict(iterations=14_000, batch_size=2, coarse_iterations=3000, densify_until_iter=10_000,
+                     opacity_reset_interval=300000)
+DYCHECK_HIDDEN = dict(kplanes_config={"grid_dimensions": 2, "input_coordinate_dim": 4, "output_coordinate_dim": 16,
+                                      "resolution": [64, 64, 64, 150]},
+                      multires=[1, 2, 4], defor_depth=1, net_width=128, plane_tv_weight=0.0002,
+                      time_smoothness_weight=0.001, l1_time_planes=0.0001)
+DYCHECK_OPT = dict(iterations=60_000, batch_size=2, coarse_iterations=3000, densify_until_iter=10_000,
+                   opacity_reset_interval=300000)
 
 
 def dynerf():
@@ -61,3 +77,11 @@ def dynerf():
 
 def dnerf():
     return model_hidden_params(**DNERF_HIDDEN), optimization_params(**DNERF_OPT)
+
+
+def hypernerf():
+    return model_hidden_params(**HYPERNERF_HIDDEN), optimization_params(**HYPERNERF_OPT)
+
+
+def dycheck():
+    return model_hidden_params(**DYCHECK_HIDDEN), optimization_params(**DYCHECK_OPT)

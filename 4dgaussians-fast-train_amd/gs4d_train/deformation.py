@@ -532,7 +532,7 @@ class _FeatureReLU(torch.autograd.Function):
     Backward in one HIP pass on the f32 MFMA (gs4d_feature_relu_backward): the ReLU mask, dx = dz W,
     dW = dz^T x and db.  Same function as Linear + ReLU (the sums run in another order: fp32 rounding)."""
 
-    shapes = ((32, 128), (64, 64), (32, 64))  # (feat_dim, W) the HIP backward is built for
+    shapes = ((32, 128), (48, 128), (64, 64), (32, 64))  # (feat_dim, W) the HIP backward is built for
 
     @staticmethod
     def forward(ctx, x, w, b):

@@ -25,7 +25,7 @@ __all__ = ["prepare", "state_at_time", "get_state_at_time", "render_view", "rend
 # (head, the flag that switches it off, GS4D_ROLE_* of include/gs4d_train.h), in forward_dynamic's order
 _HEADS = (("pos_deform", "no_dx", 0), ("scales_deform", "no_ds", 1), ("rotations_deform", "no_dr", 2),
           ("opacity_deform", "no_do", 3), ("shs_deform", "no_dshs", 4))
-_SHAPES = ((32, 128), (64, 64), (32, 64))  # (feat_dim, W) gs4d_deform_infer is built for (_FeatureReLU.shapes)
+_SHAPES = ((32, 128), (48, 128), (64, 64), (32, 64))  # (feat_dim, W) gs4d_deform_infer is built for (_FeatureReLU.shapes)
 
 
 class InferenceState:

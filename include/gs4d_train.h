@@ -338,8 +338,11 @@ int gs4d_mlp_dw_f32(int P, int KW, int W, const float *da, const float *h, float
  * h = relu(hidden).  Given g = dL/dh (P, Fout), h (P, Fout), x (P, Fin), W (Fout, Fin), one pass over the
  * rows (f32 MFMA, exact f32 products) writes what autograd forms with threshold_backward, two GEMMs and a
  * sum: dx = (g * (h > 0)) W (P, Fin), dW = (g * (h > 0))^T x (Fout, Fin), db = column sums of
- * g * (h > 0) (Fout); partial sums reduced in a fixed order.  (Fin, Fout) in {(32, 128), (64, 64),
- * (32, 64)}; contiguous; g, h, W 16-byte aligned; scratch of gs4d_feature_relu_backward_scratch_bytes. */
+ * g * (h > 0) (Fout); partial sums reduced in a fixed order.  (Fin, Fout) in {(32, 128), (48, 128), (64, 64),
+ * (32, 64)}; contiguous; g, h, W 16-byte aligned; scratch of gs4d_feature_relu_backward_scratch_bytes.
+ * (48, 128) is the HyperNeRF / DyCheck shape: multires [1, 2, 4] x output_coordinate_dim 16, net_width 128
+ * (arguments/hypernerf/default.py:5-10, arguments/dycheck/default.py:5-10); (32, 128) DyNeRF / multipleview,
+ * (64, 64) D-NeRF. */
 int gs4d_feature_relu_forward(int P, int Fin, int Fout, const float *x, const float *w, const float *b, float *h,
                               void *stream);  /* h = relu(x W^T + b), f32 MFMA; same shapes; x, W 16-byte aligned */
 /* The same, also writing h rounded to bf16 into hb (uint16 bits, (ceil(P/16)*16, Fout); its padding rows hold row
@@ -417,14 +420,16 @@ int gs4d_heads_block_forward_bf16(const gs4d_heads_block_fwd_bf16 *args, void *s
  * base through (activated when activate is set); all five outputs are always written in full.  Nothing else is
  * written: no h, no a, no deltas.  f32 MFMA, exact f32 products, each point's sums in one fixed order (the same
  * bits whatever the point's row).
- * (F, W) in {(32, 128), (64, 64), (32, 64)}; 1 <= k <= 5 heads, each role at most once, n_i = 3, 3, 4, 1, 48 for
+ * (F, W) in {(32, 128), (48, 128), (64, 64), (32, 64)} ((48, 128): the HyperNeRF / DyCheck configurations,
+ * arguments/hypernerf/default.py:5-10 and arguments/dycheck/default.py:5-10); 1 <= k <= 5 heads, each role at most
+ * once, n_i = 3, 3, 4, 1, 48 for
  * role pos, scales, rot, opacity, shs; an shs head needs K = 16.  Anything else is status 1 with a
  * gs4d_last_error() text, before any HIP call; P = 0 is a successful no-op; with no head at all the caller uses
  * gs4d_deform_tail_forward.  feat (P, F), wf (W, F), bf (W), w1 (kW, W) = the heads' first-layer weights stacked
  * in head order, b1 (kW), w2[i] (n_i, W), b2[i] (n_i); bases and outputs as gs4d_deform_tail_forward's.  feat, wf,
  * w1, w2[i], rot and shs 16-byte aligned.  GS4D_TRAIN_ERR_LDS when the device cannot give the kernel its LDS
  * (4 ((W + npad) (W + 8) + W (F + 8) + 2 W + npad) bytes, npad = the widest head's n rounded up to 16: 117,440
- * at (32, 128) with shs). */
+ * at (32, 128) with shs, 125,632 at (48, 128)). */
 enum { GS4D_ROLE_POS = 0, GS4D_ROLE_SCALES = 1, GS4D_ROLE_ROT = 2, GS4D_ROLE_OPACITY = 3, GS4D_ROLE_SHS = 4 };
 typedef struct gs4d_deform_infer_args {
     int P, F, W, K; /* points, field features, hidden width, SH coefficients */

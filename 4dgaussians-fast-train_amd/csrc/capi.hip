@@ -328,7 +328,8 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
 // gs4d_backward_ex (DEPTH = false) and gs4d_backward_depth (DEPTH = true): the same orchestration over the
 // colour-only or the depth-gradient instantiations of the three backward stages.  dL_dalpha (gs4d_backward_aux;
 // NULL for none) only changes the start value of the reverse walk's running sum, in either instantiation.
-template <bool DEPTH>
+// ABS (gs4d_backward_absgrad): the absgrad instantiations of the three stages, which also fill abs_dmean2D.
+template <bool DEPTH, bool ABS = false>
 static int backward_impl(int P, int D, int M, int R, const float *background, int width, int height,
                          const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
                          float scale_modifier, const float *rotations, const float *cov3D_precomp,
@@ -337,9 +338,11 @@ static int backward_impl(int P, int D, int M, int R, const float *background, in
                          const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
                          float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
                          float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc,
-                         void *scratch_ctx, int debug, void *stream_, int view_transposed) {
+                         void *scratch_ctx, int debug, void *stream_, int view_transposed,
+                         float *abs_dmean2D = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "backward: bad sizes");
+    if (ABS && !abs_dmean2D) return fail(GS4D_ERR_ARG, "backward_absgrad: missing abs_dmean2D");
     if (P == 0) return GS4D_OK;
     if (DEPTH && (!dL_ddepth || !dL_dpix)) return fail(GS4D_ERR_ARG, "backward_depth: missing dL_ddepth or dL_dpix");
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !means3D)
@@ -372,7 +375,11 @@ static int backward_impl(int P, int D, int M, int R, const float *background, in
     if (R > 0) {
         b = BinningState::carve(binning_buffer, R, T);
         const float *color_ptr = colors_precomp;  // NULL -> the forward's rgb (rasterizer_impl.cu:392)
-        if (DEPTH)
+        if (ABS)
+            GS4D_REPEATED_STAGE("render_backward", launch_render_backward_abs(a, g, b.gid_by_e, b.upos, img, dL_dpix,
+                                                                              DEPTH ? dL_ddepth : nullptr, dL_dalpha,
+                                                                              contrib, stream));
+        else if (DEPTH)
             GS4D_REPEATED_STAGE("render_backward", launch_render_backward_depth(a, g, b.gid_by_e, b.upos, img, dL_dpix,
                                                                                 dL_ddepth, dL_dalpha, contrib, stream));
         else
@@ -380,7 +387,14 @@ static int backward_impl(int P, int D, int M, int R, const float *background, in
                                                                           dL_dpix, dL_dalpha, contrib, stream));
     }
     const float *cov3D_ptr = cov3D_precomp ? cov3D_precomp : g.cov3D;  // rasterizer_impl.cu:414
-    if (DEPTH) {
+    if (ABS) {
+        GS4D_STAGE("contrib_reduce", launch_contrib_reduce_abs(a, g, b, R, contrib, reduce_scratch, DEPTH, dL_dmean2D,
+                                                               dconic, dL_dopacity, dL_dcolor, abs_dmean2D, stream));
+        GS4D_STAGE("gaussian_backward",
+                   launch_gaussian_backward_abs(a, g, R, reduce_scratch, DEPTH, radii_ptr, means3D, shs, scales,
+                                                rotations, cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dL_dcolor,
+                                                dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, abs_dmean2D, stream));
+    } else if (DEPTH) {
         GS4D_STAGE("contrib_reduce", launch_contrib_reduce_depth(a, g, b, R, contrib, reduce_scratch, dL_dmean2D, dconic,
                                                                  dL_dopacity, dL_dcolor, stream));
         GS4D_STAGE("gaussian_backward",
@@ -456,6 +470,31 @@ int gs4d_backward_aux(int P, int D, int M, int R, const float *background, int w
                                 tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, dL_dalpha,
                                 dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
                                 dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+}
+
+int gs4d_backward_absgrad(int P, int D, int M, int R, const float *background, int width, int height,
+                          const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                          float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                          const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                          float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer,
+                          char *image_buffer, const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha,
+                          float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D,
+                          gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
+                          int view_transposed) {
+    if (dL_ddepth)
+        return backward_impl<true, true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                         tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                         dL_ddepth, dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
+                                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch_alloc, scratch_ctx, debug,
+                                         stream, view_transposed, abs_dmean2D);
+    return backward_impl<false, true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                      scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                      tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                      nullptr, dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
+                                      dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch_alloc, scratch_ctx, debug, stream,
+                                      view_transposed, abs_dmean2D);
 }
 
 int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out_alpha, void *stream) {

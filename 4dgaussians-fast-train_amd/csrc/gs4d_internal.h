@@ -13,7 +13,8 @@ constexpr float kLog2e = 1.4426950408889634f;    // the blend kernels evaluate t
 constexpr int kPreprocessBlock = 256;           // Gaussians per preprocess / duplicate workgroup
 constexpr int kMaxDevices = 64;                 // per-device host state (the forward's readback word)
 // Per-instance gradient record written by the render backward at the instance's emission slot:
-// m2x m2y conic_a conic_b conic_c opacity r g b + 3 pad (48 bytes = three 16-byte stores)
+// m2x m2y conic_a conic_b conic_c opacity r g b, then float 9 = W3 (the depth-gradient walk), floats 10 and 11 = the
+// absolute mean2D sums (the absgrad walk); unused ones are never read (48 bytes = three 16-byte stores)
 constexpr int kContribStride = 12;
 
 // ---- scratch layouts -------------------------------------------------------------------------
@@ -219,6 +220,20 @@ hipError_t launch_gaussian_backward_depth(const Args &a, GeomState g, int R, cha
                                           float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                                           float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
                                           hipStream_t s);
+// the absgrad backward (gs4d_backward_absgrad): the three stages carrying the records' floats 10 and 11 (sums over
+// pixels of |per-pixel mean2D term|) into abs_dmean2D (P x 3); dL_ddepth != NULL / depth selects the W3 variants
+hipError_t launch_render_backward_abs(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
+                                      ImageState img, const float *dL_dpix, const float *dL_ddepth,
+                                      const float *dL_dalpha, float *contrib, hipStream_t s);
+hipError_t launch_contrib_reduce_abs(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+                                     char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
+                                     float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s);
+hipError_t launch_gaussian_backward_abs(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
+                                        const float *means3D, const float *shs, const float *scales,
+                                        const float *rotations, const float *cov3D, float *dL_dmean2D,
+                                        float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                                        float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
+                                        float *abs_dmean2D, hipStream_t s);
 size_t contrib_scratch_bytes(int R, int P);
 hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,

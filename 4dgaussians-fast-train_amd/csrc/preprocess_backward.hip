@@ -29,10 +29,17 @@ struct GradOut {
     float *color;
     const float4 *conic_opacity;
     float hw, hh;
+    float *abs_mean2D;  // (P, 3), the absgrad backward only (NULL otherwise)
 };
 // NV = 10 (the depth-gradient backward): R[9] = W3, the sum of w dL/ddepth, parked in the conic gradient's
 // unused .z slot until gaussian_grads turns it into dL/dmean3D and clears the slot.
-template <int NV>
+// ABS (the absgrad backward): R[NV], R[NV + 1] = the records' floats 10 and 11, the sums over the Gaussian's pixels
+// of |u| |d power2 / d mean| (render.hip, base-2 exponent: ln 2 brings them to the reference's power), which
+// become abs_mean2D in dL_dmeans2D's units.  NA = the number of values carried: NV + 2 with ABS.
+constexpr float kLn2 = 0.6931471805599453f;
+template <int NV, bool ABS>
+constexpr int n_acc() { return NV + (ABS ? 2 : 0); }
+template <int NV, bool ABS>
 __device__ __forceinline__ void write_grads(const GradOut &o, uint32_t g, const float *R) {
     const float4 co = o.conic_opacity[g];
     const float op = co.w;
@@ -44,6 +51,16 @@ __device__ __forceinline__ void write_grads(const GradOut &o, uint32_t g, const 
     o.color[3 * g + 0] = R[6];
     o.color[3 * g + 1] = R[7];
     o.color[3 * g + 2] = R[8];
+    if (ABS) {
+        o.abs_mean2D[3 * g + 0] = o.hw * op * (kLn2 * R[NV]);
+        o.abs_mean2D[3 * g + 1] = o.hh * op * (kLn2 * R[NV + 1]);
+        o.abs_mean2D[3 * g + 2] = 0.f;
+    }
+}
+__device__ __forceinline__ void write_zero_abs(const GradOut &o, uint32_t g) {
+    o.abs_mean2D[3 * g + 0] = 0.f;
+    o.abs_mean2D[3 * g + 1] = 0.f;
+    o.abs_mean2D[3 * g + 2] = 0.f;
 }
 __device__ __forceinline__ void write_zero_grads(const GradOut &o, uint32_t g) {
     o.mean2D[3 * g + 0] = 0.f;
@@ -55,19 +72,23 @@ __device__ __forceinline__ void write_zero_grads(const GradOut &o, uint32_t g) {
     o.color[3 * g + 1] = 0.f;
     o.color[3 * g + 2] = 0.f;
 }
-template <int NV>
+template <int NV, bool ABS>
 __device__ __forceinline__ void store9(float4 *p, const float *acc) {
     p[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
     p[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    p[2] = make_float4(acc[8], NV == 10 ? acc[NV - 1] : 0.f, 0.f, 0.f);
+    p[2] = make_float4(acc[8], NV == 10 ? acc[9] : 0.f, ABS ? acc[NV] : 0.f, ABS ? acc[NV + 1] : 0.f);
 }
-template <int NV>
+template <int NV, bool ABS>
 __device__ __forceinline__ void add9(float *acc, const float4 *p) {
     const float4 a = p[0], b = p[1], c = p[2];
     acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
     acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
     acc[8] += c.x;
-    if (NV == 10) acc[NV - 1] += c.y;
+    if (NV == 10) acc[9] += c.y;
+    if (ABS) {
+        acc[NV] += c.z;
+        acc[NV + 1] += c.w;
+    }
 }
 
 // One step of the wave's segmented inclusive scan by DPP moves (no LDS): lane l takes the (sums, flag) of
@@ -92,8 +113,9 @@ __device__ __forceinline__ void seg_scan_step(float (&acc)[NV], bool &f) {
 // slots, so a segmented inclusive scan (fixed shuffle tree) sums each Gaussian's piece of the wave.
 // Pieces that are a whole Gaussian are written out; a piece continuing from the previous wave goes
 // to part[w][0], a piece that starts a Gaussian and continues into the next wave to part[w][1];
-// e_first[g] = the Gaussian's first slot.  NV = 10 also sums the records' float 9 (W3), in the same order.
-template <int NV>
+// e_first[g] = the Gaussian's first slot.  NV = 10 also sums the records' float 9 (W3), ABS their floats 10 and 11
+// (the absolute sums), in the same order: 9, 10, 11 or 12 values ride the scan.
+template <int NV, bool ABS>
 __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *__restrict__ n_dev,
                                                                const uint32_t *__restrict__ gid_by_e,
                                                                const float4 *__restrict__ rec, GradOut o,
@@ -106,7 +128,8 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
     const int e = w * 64 + lane;
     const bool valid = e < n;
     const uint32_t key = valid ? gid_by_e[e] & kGidMask : 0xFFFFFFFFu;
-    float acc[NV];
+    constexpr int NA = n_acc<NV, ABS>();
+    float acc[NA];
     {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
         if (valid) {
@@ -117,7 +140,11 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
         acc[0] = a.x; acc[1] = a.y; acc[2] = a.z; acc[3] = a.w;
         acc[4] = b.x; acc[5] = b.y; acc[6] = b.z; acc[7] = b.w;
         acc[8] = c.x;
-        if (NV == 10) acc[NV - 1] = c.y;
+        if (NV == 10) acc[9] = c.y;
+        if (ABS) {
+            acc[NV] = c.z;
+            acc[NV + 1] = c.w;
+        }
     }
     uint32_t kp = __shfl_up(key, 1), kn = __shfl_down(key, 1);
     if (lane == 0) kp = e > 0 ? gid_by_e[e - 1] & kGidMask : 0xFFFFFFFFu;
@@ -137,9 +164,9 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
     const bool head0 = __ballot(head) & 1ull;
     if (valid && (tail || lane == 63)) {
         const bool starts = lane != fe || head0;  // the piece starts at its Gaussian's first slot
-        if (starts && tail) write_grads<NV>(o, key, acc);
-        else if (!starts) store9<NV>(part + ((size_t)w * 2) * 3, acc);
-        else store9<NV>(part + ((size_t)w * 2 + 1) * 3, acc);
+        if (starts && tail) write_grads<NV, ABS>(o, key, acc);
+        else if (!starts) store9<NV, ABS>(part + ((size_t)w * 2) * 3, acc);
+        else store9<NV, ABS>(part + ((size_t)w * 2 + 1) * 3, acc);
     }
 }
 
@@ -150,7 +177,8 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
 // projection terms returned (the caller adds the SH term, backward.cu:390, and stores it).
 // NV = 10: dL/dmean3D also takes W3 d(p_view.z)/dmean, the view matrix's depth row (forward.cu:250's
 // p_view.z = m[2] x + m[6] y + m[10] z + m[14]); culled Gaussians (radii 0) get nothing.
-template <int NV>
+// ABS: abs_mean2D of a Gaussian spanning waves comes from the same sum; zeros without instances or with radii 0.
+template <int NV, bool ABS>
 __device__ __forceinline__ V3 gaussian_grads(
     int idx, const Args &a, const GeomState &g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
@@ -161,14 +189,16 @@ __device__ __forceinline__ V3 gaussian_grads(
         const uint32_t ni = g.n_inst[idx];
         if (ni == 0) {
             write_zero_grads(o, (uint32_t)idx);
+            if (ABS) write_zero_abs(o, (uint32_t)idx);
         } else {
             const uint32_t e0 = e_first[idx], w0 = e0 >> 6, w1 = (e0 + ni - 1) >> 6;
             if (w0 != w1) {
-                float acc[NV] = {};
-                add9<NV>(acc, part + ((size_t)w0 * 2 + 1) * 3);
-                for (uint32_t w = w0 + 1; w <= w1; w++) add9<NV>(acc, part + ((size_t)w * 2) * 3);
-                write_grads<NV>(o, (uint32_t)idx, acc);
+                float acc[n_acc<NV, ABS>()] = {};
+                add9<NV, ABS>(acc, part + ((size_t)w0 * 2 + 1) * 3);
+                for (uint32_t w = w0 + 1; w <= w1; w++) add9<NV, ABS>(acc, part + ((size_t)w * 2) * 3);
+                write_grads<NV, ABS>(o, (uint32_t)idx, acc);
             }
+            if (ABS && radii[idx] <= 0) write_zero_abs(o, (uint32_t)idx);  // this thread wrote it, or pass 1 did
         }
     }
     float dcov[6] = {0, 0, 0, 0, 0, 0};
@@ -220,7 +250,7 @@ __device__ __forceinline__ V3 gaussian_grads(
 }
 
 // Without SH coefficients (colours precomputed): one thread per Gaussian, dL/dmean3D = the two terms.
-template <int NV>
+template <int NV, bool ABS>
 __global__ __launch_bounds__(256) void gaussian_backward_kernel(
     Args a, GeomState g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
@@ -229,7 +259,7 @@ __global__ __launch_bounds__(256) void gaussian_backward_kernel(
     const uint32_t *__restrict__ e_first, const float4 *__restrict__ part, GradOut o) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.P) return;
-    const V3 dmean = gaussian_grads<NV>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
+    const V3 dmean = gaussian_grads<NV, ABS>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
                                     dL_dcov3D, dL_dscale, dL_drot, e_first, part, o);
     dL_dmean3D[3 * idx + 0] = dmean.x;
     dL_dmean3D[3 * idx + 1] = dmean.y;
@@ -247,7 +277,7 @@ __global__ __launch_bounds__(256) void gaussian_backward_kernel(
 // work split at the SH part) cost one launch more.
 constexpr int kShThreads = 128, kShRow = 49;
 
-template <bool kVec4, int NV>
+template <bool kVec4, int NV, bool ABS>
 __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     Args a, GeomState g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
@@ -278,7 +308,7 @@ __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     V3 dmean = v3(0, 0, 0);
     const int idx = g0 + threadIdx.x;
     if ((int)threadIdx.x < n)  // pass 2 writes this Gaussian's dL/dcolor (when it spans waves) before it is read
-        dmean = gaussian_grads<NV>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic, dL_dcov3D,
+        dmean = gaussian_grads<NV, ABS>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic, dL_dcov3D,
                                dL_dscale, dL_drot, e_first, part, o);
     __syncthreads();
     if ((int)threadIdx.x < n) {
@@ -324,8 +354,8 @@ size_t contrib_scratch_bytes(int R, int P) {
 }
 
 static GradOut grad_out(const Args &a, GeomState g, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                        float *dL_dcolor) {
-    return GradOut{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, g.conic_opacity, 0.5f * a.W, 0.5f * a.H};
+                        float *dL_dcolor, float *abs_dmean2D = nullptr) {
+    return GradOut{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, g.conic_opacity, 0.5f * a.W, 0.5f * a.H, abs_dmean2D};
 }
 static float4 *scratch_part(char *scratch) { return (float4 *)scratch; }
 static uint32_t *scratch_e_first(char *scratch, int R) {
@@ -333,16 +363,16 @@ static uint32_t *scratch_e_first(char *scratch, int R) {
     return (uint32_t *)(scratch + align_up(nw * 2 * 3 * sizeof(float4), 256));
 }
 
-template <int NV>
+template <int NV, bool ABS = false>
 static hipError_t contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                 float *dL_dcolor, hipStream_t s) {
+                                 float *dL_dcolor, hipStream_t s, float *abs_dmean2D = nullptr) {
     if (R == 0) return hipSuccess;  // every Gaussian has n_inst = 0: gaussian_backward writes the zeros
     const size_t nw = ((size_t)R + 63) / 64;
     const uint32_t *n_dev = b.scratch;  // L' (binning.hip)
-    hipLaunchKernelGGL(contrib_segments_kernel<NV>, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, n_dev, b.gid_by_e,
-                       reinterpret_cast<const float4 *>(contrib), grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity,
-                                                                          dL_dcolor),
+    hipLaunchKernelGGL((contrib_segments_kernel<NV, ABS>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, n_dev,
+                       b.gid_by_e, reinterpret_cast<const float4 *>(contrib),
+                       grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, abs_dmean2D),
                        scratch_part(scratch), scratch_e_first(scratch, R));
     return hipGetLastError();
 }
@@ -358,22 +388,22 @@ hipError_t launch_contrib_reduce_depth(const Args &a, GeomState g, BinningState 
     return contrib_reduce<10>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s);
 }
 
-template <int NV>
+template <int NV, bool ABS = false>
 static hipError_t gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
                                     const float *means3D, const float *shs, const float *scales, const float *rotations,
                                     const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
                                     float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
-                                    float *dL_dscale, float *dL_drot, hipStream_t s) {
-    const GradOut o = grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor);
+                                    float *dL_dscale, float *dL_drot, hipStream_t s, float *abs_dmean2D = nullptr) {
+    const GradOut o = grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, abs_dmean2D);
     if (shs) {
         const bool vec4 = a.M == 16 && (((size_t)shs | (size_t)dL_dsh) & 15) == 0;
-        const auto kernel = vec4 ? gaussian_sh_backward_kernel<true, NV> : gaussian_sh_backward_kernel<false, NV>;
+        const auto kernel = vec4 ? gaussian_sh_backward_kernel<true, NV, ABS> : gaussian_sh_backward_kernel<false, NV, ABS>;
         hipLaunchKernelGGL(kernel,
                            dim3((a.P + kShThreads - 1) / kShThreads), dim3(kShThreads), 0, s, a, g, radii, means3D,
                            scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot,
                            scratch_e_first(scratch, R), scratch_part(scratch), o, shs, g.clamped, dL_dcolor, dL_dsh);
     } else {
-        hipLaunchKernelGGL(gaussian_backward_kernel<NV>, dim3((a.P + 255) / 256), dim3(256), 0, s, a, g, radii, means3D,
+        hipLaunchKernelGGL((gaussian_backward_kernel<NV, ABS>), dim3((a.P + 255) / 256), dim3(256), 0, s, a, g, radii, means3D,
                            scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D,
                            dL_dscale, dL_drot, scratch_e_first(scratch, R), scratch_part(scratch), o);
     }
@@ -395,6 +425,32 @@ hipError_t launch_gaussian_backward_depth(const Args &a, GeomState g, int R, cha
                                           hipStream_t s) {
     return gaussian_backward<10>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic,
                                  dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, s);
+}
+
+// the absgrad backward (gs4d_backward_absgrad): the same two stages carrying the records' floats 10 and 11 into
+// abs_dmean2D (P x 3); `depth` selects the instantiations that also carry W3
+hipError_t launch_contrib_reduce_abs(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+                                     char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
+                                     float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s) {
+    if (depth)
+        return contrib_reduce<10, true>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s,
+                                        abs_dmean2D);
+    return contrib_reduce<9, true>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s,
+                                   abs_dmean2D);
+}
+hipError_t launch_gaussian_backward_abs(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
+                                        const float *means3D, const float *shs, const float *scales,
+                                        const float *rotations, const float *cov3D, float *dL_dmean2D,
+                                        float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                                        float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
+                                        float *abs_dmean2D, hipStream_t s) {
+    if (depth)
+        return gaussian_backward<10, true>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
+                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                           dL_drot, s, abs_dmean2D);
+    return gaussian_backward<9, true>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
+                                      dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                      dL_drot, s, abs_dmean2D);
 }
 
 }  // namespace gs4d

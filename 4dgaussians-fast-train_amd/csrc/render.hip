@@ -506,7 +506,9 @@ __device__ __forceinline__ float dpp(float v) {
 // record float offset (from record j's start; record j + 1 follows at +12) of this lane's total.
 // DEPTH: the odd rows of x5, which hold nothing otherwise, carry the depth sum W3 = sum w dL/ddepth to
 // record float 9 (the first of the three free floats after W2).
-template <bool DEPTH>
+// ABS: a sixth register x7 = (a.AX, a.AY, b.AX, b.AY) shares x5's tree from stage B on and ends in column 6:
+// the absolute sums of the absgrad walk, record floats 10 and 11 (the record is full).
+template <bool DEPTH, bool ABS>
 __device__ __forceinline__ int red_offset(int lane) {
     const int r = lane >> 4, c = lane & 15, splat = (r >> 1) * 12, odd = r & 1;
     switch (c) {
@@ -515,12 +517,14 @@ __device__ __forceinline__ int red_offset(int lane) {
     case 8: return splat + (odd ? 6 : 5);   // x2: S u yl^2, W0
     case 12: return splat + (odd ? 4 : 1);  // x4: S dx u yl, S dx u
     case 2: return odd ? (DEPTH ? splat + 9 : -1) : splat + 3;  // x5: S dx^2 u (odd rows: W3 or nothing)
+    case 6: return ABS ? splat + (odd ? 11 : 10) : -1;          // x7: S |u fx|, S |u fy|
     default: return -1;
     }
 }
-template <bool DEPTH>
+template <bool DEPTH, bool ABS>
 __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const SplatPart &b, float dxa, float dxb,
-                                                     float w3a, float w3b, float *rec_pair, int lane, int roff) {
+                                                     float w3a, float w3b, float axa, float aya, float axb, float ayb,
+                                                     float *rec_pair, int lane, int roff) {
     const float h0 = swap32_add(a.u0, b.u0);  // lanes 0-31: a, 32-63: b
     const float h1 = swap32_add(a.u1, b.u1);
     const float h2 = swap32_add(a.u2, b.u2);
@@ -548,7 +552,16 @@ __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const S
     }
     // stage B (half-row mirror): z12 | z34 -> w
     const float w = (c4 ? z12 : z34) + dpp<0x141>(c4 ? z34 : z12);
-    const float w5 = z5 + dpp<0x141>(z5);
+    float w5;
+    if (ABS) {
+        // x7 takes its own stage A (sums only, no product) and the half of z5's stage B that carried copies: the
+        // columns with bit 2 clear keep x5's sums in x5's order (the bits of S dx^2 u and W3 stay), the others x7's
+        const float x7 = swap16_add(swap32_add(axa, axb), swap32_add(aya, ayb));
+        const float z7 = x7 + dpp<0x128>(x7);
+        w5 = (c4 ? z5 : z7) + dpp<0x141>(c4 ? z7 : z5);
+    } else {
+        w5 = z5 + dpp<0x141>(z5);
+    }
     // stage C (c ^ 2): w | w5 -> v; stage D (c ^ 1)
     const float v = (c2 ? w : w5) + dpp<0x4E>(c2 ? w5 : w);  // quad_perm [2, 3, 0, 1]
     const float u = v + dpp<0xB1>(v);                         // quad_perm [1, 0, 3, 2]
@@ -578,6 +591,7 @@ struct BwdPixels {
 // The per-splat half of a step: falloff, the reference's skip decisions and alpha.
 struct HalfAlpha {
     f2 ale, ae, om;  // o G with the skips applied, alpha, 1 - alpha
+    f2 dy;           // mean row - pixel row (read by the absgrad walk only)
 };
 template <bool ALL, bool GEN>
 __device__ __forceinline__ HalfAlpha half_alpha(const f2 Y2, const f2 C2, const f2 O2, const f2 pa2, const f2 pb2,
@@ -601,6 +615,7 @@ __device__ __forceinline__ HalfAlpha half_alpha(const f2 Y2, const f2 C2, const 
     }
     // the skip applied to o G: a skipped pixel has alpha 0 exactly
     HalfAlpha h;
+    h.dy = dy;
     h.ale = f2{k0 ? al.x : 0.f, k1 ? al.y : 0.f};
     h.ae = GEN ? f2{fminf(0.99f, h.ale.x), fminf(0.99f, h.ale.y)} : h.ale;
     h.om = bc2(1.f) - h.ae;
@@ -609,11 +624,18 @@ __device__ __forceinline__ HalfAlpha half_alpha(const f2 Y2, const f2 C2, const 
 // The rest of a step once the splat's T (the transmittance in front of it, Tn) is known.
 // DEPTH: diff gains d_g dL/ddepth as its last term (dL/ddepth = 0 leaves every value as it was) and
 // U[6] = W3 accumulates w dL/ddepth.
-template <bool GEN, int NU>
+// ABS (absgrad): the pixel's pull on the 2-D mean is u' times the exponent's slope, d power2 / d mean =
+// (fx, fy) = (2 geo.z dx + geo.w dy, geo.w dx + 2 opc.x dy) = -log2e (a dx + b dy, b dx + c dy) (backward.cu:
+// 541-546); the last two sums take |u'| |fx| and |u'| |fy| -- plain v_fma_f32 with |src| modifiers, packed f32
+// has none.  A skipped pixel has u' = 0 and adds an exact 0.  Nothing else reads fx, fy.
+struct AbsOps {
+    f2 QX2, BW2, CC2;  // 2 geo.z dx (per lane), geo.w, 2 opc.x; pb2 = geo.w dx is the falloff's own
+};
+template <bool GEN, bool DEPTH, bool ABS, int NU>
 __device__ __forceinline__ void half_accum(const HalfAlpha &h, const f2 Tn, f2 &A, const f2 dp0, const f2 dp1,
                                            const f2 dp2, const f2 dd, const f2 R2, const f2 G2, const f2 B2,
-                                           const f2 D2, f2 yl, f2 yl2, f2 (&U)[NU]) {
-    constexpr bool DEPTH = NU == 7;
+                                           const f2 D2, const f2 pb2, const AbsOps &ao, f2 yl, f2 yl2, f2 (&U)[NU]) {
+    static_assert(NU == 6 + (DEPTH ? 1 : 0) + (ABS ? 2 : 0), "sums: 6, W3 with DEPTH, then the two absolute sums");
     f2 &U0 = U[0], &U1 = U[1], &U2 = U[2], &W0 = U[3], &W1 = U[4], &W2 = U[5];
     f2 diff = fma2(B2, dp2, fma2(G2, dp1, fma2(R2, dp0, -A)));  // c . dL/dpix - accum_rec . dL/dpix
     if (DEPTH) diff = fma2(D2, dd, diff);                        // + d_g dL/ddepth
@@ -628,7 +650,15 @@ __device__ __forceinline__ void half_accum(const HalfAlpha &h, const f2 Tn, f2 &
     W0 = fma2(w, dp0, W0);
     W1 = fma2(w, dp1, W1);
     W2 = fma2(w, dp2, W2);
-    if (DEPTH) U[NU - 1] = fma2(w, dd, U[NU - 1]);
+    if (DEPTH) U[6] = fma2(w, dd, U[6]);
+    if (ABS) {
+        const f2 fx = fma2(ao.BW2, h.dy, ao.QX2), fy = fma2(ao.CC2, h.dy, pb2);
+        f2 &AX = U[NU - 2], &AY = U[NU - 1];
+        AX.x = fmaf(fabsf(u.x), fabsf(fx.x), AX.x);
+        AX.y = fmaf(fabsf(u.y), fabsf(fx.y), AX.y);
+        AY.x = fmaf(fabsf(u.x), fabsf(fy.x), AY.x);
+        AY.y = fmaf(fabsf(u.y), fabsf(fy.y), AY.y);
+    }
 }
 // One half tile of one splat of the reverse walk: updates the half's pixel state and adds its
 // per-lane partial sums (moments of u' = o G dL/dalpha in the tile-centred row coordinate yl -- the
@@ -646,8 +676,9 @@ struct SplatOps {
     f2 Y2, C2, O2, R2, G2, B2, D2, pa2, pb2;  // D2 = the view depth (read by the depth-gradient walk only)
     bool chk;
     uint32_t contributor;
+    AbsOps ao;  // read by the absgrad walk only
 };
-template <bool ALL, bool GEN, int NU>
+template <bool ALL, bool GEN, bool DEPTH, bool ABS, int NU>
 __device__ __forceinline__ void half_step(f2 &T, f2 &A, const f2 dp0, const f2 dp1, const f2 dp2, const f2 dd,
                                           const SplatOps &s, f2 yl, f2 yl2, uint32_t last0, uint32_t last1,
                                           f2 (&U)[NU]) {
@@ -655,9 +686,9 @@ __device__ __forceinline__ void half_step(f2 &T, f2 &A, const f2 dp0, const f2 d
     const f2 inv = f2{__builtin_amdgcn_rcpf(h.om.x), __builtin_amdgcn_rcpf(h.om.y)};
     const f2 Tn = T * inv;  // backward.cu:503
     T = Tn;
-    half_accum<GEN>(h, Tn, A, dp0, dp1, dp2, dd, s.R2, s.G2, s.B2, s.D2, yl, yl2, U);
+    half_accum<GEN, DEPTH, ABS>(h, Tn, A, dp0, dp1, dp2, dd, s.R2, s.G2, s.B2, s.D2, s.pb2, s.ao, yl, yl2, U);
 }
-template <bool ALL, bool GEN, int NU>
+template <bool ALL, bool GEN, bool DEPTH, bool ABS, int NU>
 __device__ __forceinline__ void half_pair_step(f2 &T, f2 &A, const f2 dp0, const f2 dp1, const f2 dp2, const f2 dd,
                                                const SplatOps &sa, const SplatOps &sb, f2 yl, f2 yl2, uint32_t last0,
                                                uint32_t last1, f2 (&Ua)[NU], f2 (&Ub)[NU]) {
@@ -669,24 +700,27 @@ __device__ __forceinline__ void half_pair_step(f2 &T, f2 &A, const f2 dp0, const
     const f2 r = f2{__builtin_amdgcn_rcpf(prod.x), __builtin_amdgcn_rcpf(prod.y)};
     const f2 Tb = T * r;         // backward.cu:503 twice: T / (1 - alpha_a) / (1 - alpha_b)
     const f2 Ta = Tb * hb.om;    // T / (1 - alpha_a)
-    half_accum<GEN>(ha, Ta, A, dp0, dp1, dp2, dd, sa.R2, sa.G2, sa.B2, sa.D2, yl, yl2, Ua);
-    half_accum<GEN>(hb, Tb, A, dp0, dp1, dp2, dd, sb.R2, sb.G2, sb.B2, sb.D2, yl, yl2, Ub);
+    half_accum<GEN, DEPTH, ABS>(ha, Ta, A, dp0, dp1, dp2, dd, sa.R2, sa.G2, sa.B2, sa.D2, sa.pb2, sa.ao, yl, yl2, Ua);
+    half_accum<GEN, DEPTH, ABS>(hb, Tb, A, dp0, dp1, dp2, dd, sb.R2, sb.G2, sb.B2, sb.D2, sb.pb2, sb.ao, yl, yl2, Ub);
     T = Tb;
 }
 
 constexpr int kBwdDepthWaves = 4;  // waves per SIMD of the depth-gradient instantiation (<= 128 VGPRs)
 // 4 waves per SIMD (<= 128 VGPRs, no spills): the reach-combo blocks hold at most the four falloff chains
 // of one pair.  DEPTH (gs4d_backward_depth): dL/ddepth joins the walk as a fourth channel; its extra
-// per-pixel state, operands and sums are kBwdDepthWaves's business.
-template <bool DEPTH>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwdDepthWaves : 4, DEPTH ? kBwdDepthWaves : 4))) void render_backward_kernel(Args a, const uint2 *__restrict__ ranges, const uint32_t *__restrict__ order,
+// per-pixel state, operands and sums are kBwdDepthWaves's business.  ABS (gs4d_backward_absgrad):
+// two more sums per splat and their three operands, with or without DEPTH.
+constexpr int kBwdAbsWaves = 3;  // waves per SIMD of the two absgrad instantiations (<= 168 VGPRs)
+constexpr int bwd_waves(bool depth, bool abs) { return abs ? kBwdAbsWaves : depth ? kBwdDepthWaves : 4; }
+template <bool DEPTH, bool ABS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_waves(DEPTH, ABS), bwd_waves(DEPTH, ABS)))) void render_backward_kernel(Args a, const uint2 *__restrict__ ranges, const uint32_t *__restrict__ order,
                             const uint32_t *__restrict__ gid_by_e,
                             const uint32_t *__restrict__ upos, const float4 *__restrict__ splat,
                             const float *__restrict__ final_Ts,
                             const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpixels,
                             const float *__restrict__ dL_ddepths, const float *__restrict__ dL_dalphas,
                             float *__restrict__ contrib) {
-    constexpr int NU = DEPTH ? 7 : 6;
+    constexpr int NU = 6 + (DEPTH ? 1 : 0) + (ABS ? 2 : 0);
     __shared__ SplatLDS s_sp[64];
     __shared__ float4 s_rec[64][3];  // reduced sums of the batch's splats
     const int tile = (int)__builtin_amdgcn_readfirstlane(order[blockIdx.x]);  // longest runs first
@@ -706,7 +740,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
     const f2 yl[2] = {f2{ylane, ylane + 4.f}, f2{ylane + 8.f, ylane + 12.f}};
     const f2 yl2[2] = {yl[0] * yl[0], yl[1] * yl[1]};
     const float yc = (float)(ty * kBlockY) + 7.5f;
-    const int roff = red_offset<DEPTH>(lane);
+    const int roff = red_offset<DEPTH, ABS>(lane);
 
     BwdPixels st;
     uint32_t lastc[4];
@@ -840,23 +874,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
             for (int i = 0; i < 2; i++)
                 so[i] = SplatOps{bc2(geo[i].y), bc2(opc[i].x), bc2(opc[i].w), bc2(col[i].x), bc2(col[i].y),
                                  bc2(col[i].z), bc2(col[i].w), bc2(pa[i]), bc2(pb[i]), ((nonpd >> (j + i)) & 1) != 0,
-                                 (uint32_t)(end - 1 - (j + i))};
+                                 (uint32_t)(end - 1 - (j + i)),
+                                 AbsOps{bc2(2.f * geo[i].z * dxs[i]), bc2(geo[i].w), bc2(2.f * opc[i].x)}};
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 if (M[h] == 3)
-                    half_pair_step<ALL, GEN>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], st.dd[h], so[0], so[1],
-                                             yl[h], yl2[h], lastc[2 * h], lastc[2 * h + 1], U[0], U[1]);
+                    half_pair_step<ALL, GEN, DEPTH, ABS>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], st.dd[h],
+                                                         so[0], so[1], yl[h], yl2[h], lastc[2 * h], lastc[2 * h + 1],
+                                                         U[0], U[1]);
                 else if (M[h] != 0)
-                    half_step<ALL, GEN>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], st.dd[h], so[M[h] >> 1],
-                                        yl[h], yl2[h], lastc[2 * h], lastc[2 * h + 1], U[M[h] >> 1]);
+                    half_step<ALL, GEN, DEPTH, ABS>(st.T[h], st.A[h], st.dp0[h], st.dp1[h], st.dp2[h], st.dd[h],
+                                                    so[M[h] >> 1], yl[h], yl2[h], lastc[2 * h], lastc[2 * h + 1],
+                                                    U[M[h] >> 1]);
             }
 #pragma unroll
             for (int i = 0; i < 2; i++)
                 part[i] = SplatPart{hsum(U[i][0]), hsum(U[i][1]), hsum(U[i][2]), hsum(U[i][3]), hsum(U[i][4]),
                                     hsum(U[i][5])};
-            wave_sum_pair_to_lds<DEPTH>(part[0], part[1], dxs[0], dxs[1], DEPTH ? hsum(U[0][NU - 1]) : 0.f,
-                                        DEPTH ? hsum(U[1][NU - 1]) : 0.f, reinterpret_cast<float *>(s_rec[j]), lane,
-                                        roff);
+            wave_sum_pair_to_lds<DEPTH, ABS>(part[0], part[1], dxs[0], dxs[1], DEPTH ? hsum(U[0][6]) : 0.f,
+                                             DEPTH ? hsum(U[1][6]) : 0.f, ABS ? hsum(U[0][NU - 2]) : 0.f,
+                                             ABS ? hsum(U[0][NU - 1]) : 0.f, ABS ? hsum(U[1][NU - 2]) : 0.f,
+                                             ABS ? hsum(U[1][NU - 1]) : 0.f, reinterpret_cast<float *>(s_rec[j]),
+                                             lane, roff);
         };
         using I3 = std::integral_constant<int, 3>;
         auto walk_batch = [&](auto all) {
@@ -900,7 +939,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
             const float4 r0 = s_rec[lane][0], r1 = s_rec[lane][1], r2 = s_rec[lane][2];
             const float my_l = s_sp[lane].geo.y;  // this lane's splat, my - yc
             const float io = s_sp[lane].opc.z;    // 1 / o: the moments were taken on u' = o u
-            // r0 = (S u, S dx u, S u yl, S dx^2 u), r1 = (S dx u yl, S u yl^2, W0, W1), r2 = (W2, W3 or -, -, -)
+            // r0 = (S u, S dx u, S u yl, S dx^2 u), r1 = (S dx u yl, S u yl^2, W0, W1),
+            // r2 = (W2, W3 or -, S |u fx| or -, S |u fy| or -)
             const float s_u = r0.x, s_uyl = r0.z;
             const float v2 = my_l * s_u - s_uyl;                 // S u dy
             const float v4 = my_l * r0.y - r1.x;                 // S dx u dy
@@ -908,7 +948,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEPTH ? kBwd
             float4 *rec = reinterpret_cast<float4 *>(contrib + (size_t)ucur * kContribStride);
             rec[0] = make_float4(s_u * io, r0.y * io, v2 * io, r0.w * io);
             rec[1] = make_float4(v4 * io, v5 * io, r1.z, r1.w);
-            rec[2] = r2;
+            rec[2] = ABS ? make_float4(r2.x, r2.y, r2.z * io, r2.w * io) : r2;  // the absolute sums are u' sums too
         }
     }
 }
@@ -919,8 +959,8 @@ hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gi
                                   float *contrib, hipStream_t s) {
     const int T = a.gx * a.gy;
     (void)colors;  // the splat records hold the colours the forward blended (colors_precomp or SH)
-    hipLaunchKernelGGL(render_backward_kernel<false>, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e,
-                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, dL_dalpha, contrib);
+    hipLaunchKernelGGL((render_backward_kernel<false, false>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
+                       gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, dL_dalpha, contrib);
     return hipGetLastError();
 }
 // the same walk with dL/ddepth (H x W): every record also carries W3 in float 9
@@ -928,8 +968,23 @@ hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32
                                         ImageState img, const float *dL_dpix, const float *dL_ddepth,
                                         const float *dL_dalpha, float *contrib, hipStream_t s) {
     const int T = a.gx * a.gy;
-    hipLaunchKernelGGL(render_backward_kernel<true>, dim3(T), dim3(64), 0, s, a, img.ranges, img.order, gid_by_e,
-                       upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha, contrib);
+    hipLaunchKernelGGL((render_backward_kernel<true, false>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
+                       gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha, contrib);
+    return hipGetLastError();
+}
+
+// the absgrad walk (gs4d_backward_absgrad): every record also carries the absolute sums in floats 10 and 11;
+// dL_ddepth (NULL for none) selects the depth instantiation
+hipError_t launch_render_backward_abs(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
+                                      ImageState img, const float *dL_dpix, const float *dL_ddepth,
+                                      const float *dL_dalpha, float *contrib, hipStream_t s) {
+    const int T = a.gx * a.gy;
+    if (dL_ddepth)
+        hipLaunchKernelGGL((render_backward_kernel<true, true>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
+                           gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha, contrib);
+    else
+        hipLaunchKernelGGL((render_backward_kernel<false, true>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
+                           gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, dL_dalpha, contrib);
     return hipGetLastError();
 }
 

@@ -132,7 +132,8 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
                            const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix, const float tan_fovx,
                            const float tan_fovy, const torch::Tensor &dL_dout_color, const torch::Tensor &sh,
                            const int degree, const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
-                           const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug) {
+                           const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug,
+                           torch::Tensor *abs_out = nullptr) {
     if (!means3D.is_cuda()) throw std::runtime_error("means3D must be a HIP (GPU) tensor; the MI355X rasterizer has no CPU path");
     const auto dev = means3D.device();
     c10::hip::HIPGuard guard(dev.index());
@@ -150,6 +151,7 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
     torch::Tensor dL_dsh = torch::empty({P, M, 3}, opts);
     torch::Tensor dL_dscales = torch::empty({P, 3}, opts);
     torch::Tensor dL_drotations = torch::empty({P, 4}, opts);
+    if (abs_out) *abs_out = torch::empty({P, 3}, opts);  // gs4d_backward_absgrad writes every row
     if (P != 0) {
         auto bg = prep(background, "bg", dev), m3 = prep(means3D, "means3D", dev), col = prep(colors, "colors_precomp", dev),
              sc = prep(scales, "scales", dev), rot = prep(rotations, "rotations", dev),
@@ -181,7 +183,15 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
         char *image = reinterpret_cast<char *>(imageBuffer.data_ptr());
         float *dsh = M ? dL_dsh.data_ptr<float>() : nullptr;
         int st;
-        if (dL_dout_alpha)
+        if (abs_out)
+            st = gs4d_backward_absgrad(
+                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
+                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
+                dd.defined() ? fptr(dd) : nullptr, da.defined() ? fptr(da) : nullptr, dL_dmeans2D.data_ptr<float>(),
+                nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
+                dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
+                abs_out->data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
+        else if (dL_dout_alpha)
             st = gs4d_backward_aux(
                 P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
                 fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
@@ -204,7 +214,8 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
                 dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
                 dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(),
                 dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
-        check_status(st, dL_dout_alpha   ? "rasterize_gaussians_backward_aux"
+        check_status(st, abs_out         ? "rasterize_gaussians_backward_absgrad"
+                         : dL_dout_alpha ? "rasterize_gaussians_backward_aux"
                          : dL_dout_depth ? "rasterize_gaussians_backward_depth"
                                          : "rasterize_gaussians_backward");
     }
@@ -256,6 +267,28 @@ RasterizeGaussiansBackwardAux(const torch::Tensor &background, const torch::Tens
     return BackwardImpl(&dL_dout_depth, &dL_dout_alpha, background, means3D, radii, colors, scales, rotations,
                         scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                         degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug);
+}
+
+// rasterize_gaussians_backward_aux's arguments; returns its tuple plus the (P, 3) absolute screen-space gradient
+// (gs4d_backward_absgrad): sums over pixels of |per-pixel mean2D term|, in dL_dmeans2D's units
+using AbsgradTuple = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+                                torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+AbsgradTuple
+RasterizeGaussiansBackwardAbsgrad(const torch::Tensor &background, const torch::Tensor &means3D,
+                                  const torch::Tensor &radii, const torch::Tensor &colors, const torch::Tensor &scales,
+                                  const torch::Tensor &rotations, const float scale_modifier,
+                                  const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+                                  const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy,
+                                  const torch::Tensor &dL_dout_color, const torch::Tensor &dL_dout_depth,
+                                  const torch::Tensor &dL_dout_alpha, const torch::Tensor &sh, const int degree,
+                                  const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
+                                  const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer,
+                                  const bool debug) {
+    torch::Tensor absgrad;
+    auto t = BackwardImpl(&dL_dout_depth, &dL_dout_alpha, background, means3D, radii, colors, scales, rotations,
+                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                          degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, &absgrad);
+    return std::tuple_cat(std::move(t), std::make_tuple(absgrad));
 }
 
 // the alpha image 1 - T_final (1, H, W) of the forward that filled imageBuffer: gs4d_alpha_image
@@ -333,6 +366,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
     m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);
     m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux);
+    m.def("rasterize_gaussians_backward_absgrad", &RasterizeGaussiansBackwardAbsgrad);
     m.def("alpha_image", &AlphaImage);
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });

@@ -8,11 +8,13 @@ Public surface identical to the reference package
   rasterize_gaussians            functional entry (:21-42)
   _RasterizeGaussians            torch.autograd.Function (:44-155)
 
-so gaussian_renderer/__init__.py and train.py run unchanged.  Two opt-in extensions, off by default:
+so gaussian_renderer/__init__.py and train.py run unchanged.  Three opt-in extensions, off by default:
 depth_grad=True (rasterize_gaussians, GaussianRasterizer) selects _RasterizeGaussiansDepth, whose backward
 also back-propagates the depth image's gradient, which the reference drops (:100-101); alpha=True selects
 _RasterizeGaussiansAux, which also returns the accumulated-alpha image 1 - T_final (1, H, W) as a fourth,
-differentiable output (the reference returns no such image, :98).  The compute runs in libgs4d (HIP
+differentiable output (the reference returns no such image, :98); absgrad=True selects the _RasterizeGaussians*Abs
+Functions, whose backward also leaves the absolute screen-space gradient (AbsGS; gsplat's `absgrad`) in
+`means2D.absgrad`, a (P, 3) tensor overwritten by every backward call.  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
 without the built extension raises ImportError -- there is no CPU fallback.
 """
@@ -24,7 +26,9 @@ import torch.nn as nn
 from . import _C  # noqa: F401  (fails loudly when the HIP extension is missing)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansDepth", "_RasterizeGaussiansAux", "_RasterizeGaussiansAuxDepth"]
+           "_RasterizeGaussiansDepth", "_RasterizeGaussiansAux", "_RasterizeGaussiansAuxDepth",
+           "_RasterizeGaussiansAbs", "_RasterizeGaussiansAbsDepth", "_RasterizeGaussiansAuxAbs",
+           "_RasterizeGaussiansAuxDepthAbs"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -61,9 +65,16 @@ def _invoke(fn, args, debug, dump_name, stage):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_grad=False, alpha=False):
-    """(color, radii, depth), or with alpha=True (color, radii, depth, alpha)"""
-    if alpha:
+                        raster_settings, depth_grad=False, alpha=False, absgrad=False):
+    """(color, radii, depth), or with alpha=True (color, radii, depth, alpha).  absgrad=True: the backward also
+    assigns `means2D.absgrad` (P, 3): per Gaussian the sum over its pixels of |the pixel's term of means2D.grad|
+    in x and y (column 2 is 0), where means2D.grad holds the signed sum."""
+    if absgrad:
+        if alpha:
+            fn = _RasterizeGaussiansAuxDepthAbs if depth_grad else _RasterizeGaussiansAuxAbs
+        else:
+            fn = _RasterizeGaussiansAbsDepth if depth_grad else _RasterizeGaussiansAbs
+    elif alpha:
         fn = _RasterizeGaussiansAuxDepth if depth_grad else _RasterizeGaussiansAux
     else:
         fn = _RasterizeGaussiansDepth if depth_grad else _RasterizeGaussians
@@ -195,14 +206,90 @@ def _aux_backward(ctx, grad_out_color, grad_depth, grad_alpha):
     return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
 
 
+class _RasterizeGaussiansAbs(torch.autograd.Function):
+    """_RasterizeGaussians whose backward also assigns means2D.absgrad (opt-in: absgrad=True)."""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        return _abs_forward(ctx, False, False, *inputs)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
+        return _abs_backward(ctx, grad_out_color, grad_depth, grad_alpha)
+
+
+class _RasterizeGaussiansAbsDepth(torch.autograd.Function):
+    """_RasterizeGaussiansDepth with means2D.absgrad (absgrad=True, depth_grad=True)."""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        return _abs_forward(ctx, True, False, *inputs)
+
+    backward = staticmethod(_RasterizeGaussiansAbs.backward)
+
+
+class _RasterizeGaussiansAuxAbs(torch.autograd.Function):
+    """_RasterizeGaussiansAux with means2D.absgrad (absgrad=True, alpha=True)."""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        return _abs_forward(ctx, False, True, *inputs)
+
+    backward = staticmethod(_RasterizeGaussiansAbs.backward)
+
+
+class _RasterizeGaussiansAuxDepthAbs(torch.autograd.Function):
+    """_RasterizeGaussiansAuxDepth with means2D.absgrad (absgrad=True, alpha=True, depth_grad=True)."""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        return _abs_forward(ctx, True, True, *inputs)
+
+    backward = staticmethod(_RasterizeGaussiansAbs.backward)
+
+
+def _abs_forward(ctx, depth_grad, alpha, means3D, means2D, *rest):
+    # the forwards of the Functions without absgrad: the same launches and saved tensors
+    if alpha:
+        out = _aux_forward(ctx, depth_grad, means3D, means2D, *rest)
+    else:
+        out = _RasterizeGaussians.forward(ctx, means3D, means2D, *rest)
+        ctx.depth_grad = depth_grad
+    ctx.absgrad_target = means2D  # the caller's tensor: the backward assigns its .absgrad
+    return out
+
+
+def _abs_backward(ctx, grad_out_color, grad_depth, grad_alpha):
+    s = ctx.raster_settings
+    if not ctx.depth_grad:
+        grad_depth = None
+    if grad_out_color is None and grad_depth is None and grad_alpha is None:
+        return (None,) * 9
+    (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
+     img_buf) = ctx.saved_tensors
+    if grad_out_color is None:
+        grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
+    none = torch.empty(0, dtype=torch.float32, device=means3D.device)  # "no such gradient"
+    # _C.rasterize_gaussians_backward_aux's positional order; one more tensor comes back
+    args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color,
+            none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha, sh, s.sh_degree,
+            s.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
+    (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations, absgrad) = _invoke(
+        _C.rasterize_gaussians_backward_absgrad, args, s.debug, "snapshot_bw.dump", "backward")
+    ctx.absgrad_target.absgrad = absgrad  # overwritten per backward call (gsplat's convention)
+    return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+
+
 def _empty_if_none(t):
     # "not provided" travels as an empty tensor (reference :197-207)
     return torch.Tensor([]) if t is None else t
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings, depth_grad=False, alpha=False):
+    def __init__(self, raster_settings, depth_grad=False, alpha=False, absgrad=False):
         super().__init__()
+        self.absgrad = absgrad  # opt-in: the backward assigns means2D.absgrad (_RasterizeGaussians*Abs)
         self.raster_settings = raster_settings
         self.depth_grad = depth_grad  # opt-in: the depth image's gradient flows back (_RasterizeGaussiansDepth)
         self.alpha = alpha  # opt-in: forward also returns the alpha image 1 - T_final (_RasterizeGaussiansAux)
@@ -223,4 +310,5 @@ class GaussianRasterizer(nn.Module):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, _empty_if_none(shs), _empty_if_none(colors_precomp), opacities,
                                    _empty_if_none(scales), _empty_if_none(rotations), _empty_if_none(cov3D_precomp),
-                                   self.raster_settings, depth_grad=self.depth_grad, alpha=self.alpha)
+                                   self.raster_settings, depth_grad=self.depth_grad, alpha=self.alpha,
+                                   absgrad=self.absgrad)

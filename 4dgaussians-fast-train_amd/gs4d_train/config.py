@@ -34,7 +34,11 @@ def optimization_params(**over):
              opacity_threshold_coarse=0.005, opacity_threshold_fine_init=0.005, opacity_threshold_fine_after=0.005,
              batch_size=1, add_point=False,
              lambda_depth=0.0,  # this build's opt-in: weight of the depth L1 on (camera, gt, gt_depth) views (train.py)
-             lambda_mask=0.0)  # opt-in: weight of mean |alpha - gt_mask| on (camera, gt, gt_depth or None, gt_mask) views
+             lambda_mask=0.0,  # opt-in: weight of mean |alpha - gt_mask| on (camera, gt, gt_depth or None, gt_mask) views
+             # opt-in (AbsGS): densify on the absolute screen-space gradient, sum over pixels of |per-pixel term|, in
+             # place of the norm of the signed sum (train.py).  The thresholds stay the user's: AbsGS roughly doubles
+             # densify_grad_threshold_* (0.0004 where the signed gradient uses 0.0002)
+             densify_absgrad=False)
     d.update(over)
     return SimpleNamespace(**d)
 

@@ -220,7 +220,9 @@ class GaussianModel:
     # ---- densification statistics (gaussian_model.py:521-523, train.py:346-349)
     def add_densification_stats(self, viewspace_grad, update_filter, radii=None):
         """xyz_gradient_accum[f] += |grad[f, :2]|, denom[f] += 1 and (when radii is given, train.py:348)
-        max_radii2D[f] = max(max_radii2D[f], radii[f]).  update_filter None: f = radii > 0 (train.py:229-232)."""
+        max_radii2D[f] = max(max_radii2D[f], radii[f]).  update_filter None: f = radii > 0 (train.py:229-232).
+        viewspace_grad is any (P, 3) tensor: the views' summed means2D.grad, or with opt.densify_absgrad their summed
+        means2D.absgrad (train_step hands over one or the other; both statistics paths just read it)."""
         if self.fused:
             from .kernels import densify_stats
             densify_stats(viewspace_grad, update_filter, radii, self.xyz_gradient_accum, self.denom, self.max_radii2D)

@@ -19,7 +19,15 @@ Mask supervision (opt-in as well): with opt.lambda_mask != 0 a view given as (ca
 gt_mask) is rendered with alpha=True and adds lambda_mask * mean |alpha - gt_mask|, alpha being the rasterizer's
 accumulated-alpha image 1 - T_final.  Such a view's depth and mask terms come from one fused kernel pair on the
 fused path (kernels.aux_loss_and_grad); views without a mask take the code they took before.
+
+Absolute-gradient densification (opt-in, AbsGS): with opt.densify_absgrad every view is rendered with absgrad=True
+and the densification statistics accumulate the norm of the views' summed `viewspace_points.absgrad[:, :2]` --
+per Gaussian the sum over its pixels of |the pixel's pull on the 2-D mean| -- in place of the norm of the signed
+sum `viewspace_points.grad`, which cancels for a large blurry Gaussian pulled both ways.  The thresholds are the
+user's: AbsGS roughly doubles densify_grad_threshold_* (0.0004 for the reference's 0.0002).
 """
+import functools
+
 import torch
 
 from . import dp
@@ -44,7 +52,8 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
 
     render_fn(camera, gaussians, debug, bg, stage=...) -> render()'s dict; defaults to
     gs4d_train.render.render (the HIP rasterizer).  The multi-process CPU tests pass a torch stand-in.  It is
-    called with depth_grad=True and / or alpha=True only for the views that need them."""
+    called with depth_grad=True and / or alpha=True only for the views that need them, and with absgrad=True for
+    every view when opt.densify_absgrad is on (its viewspace_points must then carry .absgrad after the backward)."""
     if render_fn is None:
         from .render import render as render_fn
     fused = gaussians.fused if fused_loss is None else fused_loss
@@ -57,6 +66,9 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     lambda_mask = getattr(opt, "lambda_mask", 0.0)
     depths, gt_depths = [], []  # of the views that carry a gt depth, when lambda_depth != 0
     masked = []  # (depth or None, gt_depth or None, alpha, gt_mask) of the views that carry a mask, when lambda_mask != 0
+    densify_absgrad = bool(getattr(opt, "densify_absgrad", False))
+    if densify_absgrad:
+        render_fn = functools.partial(render_fn, absgrad=True)
     for v in mine:
         cam, gt = views[v][0], views[v][1]
         has_depth = lambda_depth != 0 and len(views[v]) > 2 and views[v][2] is not None
@@ -199,6 +211,22 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
         for t in vs_list:
             if t.grad is not None:
                 viewspace_grad = viewspace_grad + t.grad
+    if densify_absgrad:
+        # the densification signal: the views' absolute gradients, summed like their signed ones (which still
+        # reach the parameters through autograd; only the statistics read this tensor)
+        abs_list = []
+        for t in vs_list:
+            if t.grad is not None:  # this view's rasterizer backward ran
+                if getattr(t, "absgrad", None) is None:
+                    raise RuntimeError("opt.densify_absgrad: render_fn's viewspace_points carries no .absgrad after the "
+                                       "backward; render_fn must honour absgrad=True (gs4d_train.render.render does)")
+                abs_list.append(t.absgrad)
+        if len(abs_list) == 1:
+            viewspace_grad = abs_list[0]
+        else:
+            viewspace_grad = torch.zeros_like(gaussians.get_xyz)
+            for t in abs_list:
+                viewspace_grad = viewspace_grad + t
     # the returned loss: a view when nothing writes it later (the data-parallel all-reduce sums in place)
     loss_out = loss.detach().reshape(1)
     if data_parallel:

@@ -152,6 +152,35 @@ int gs4d_backward_aux(int P, int D, int M, int R, const float *background, int w
                       float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
                       int debug, void *stream, int view_transposed);
 
+/* gs4d_backward_aux that also returns the absolute screen-space gradient (AbsGS; gsplat's `absgrad`; no reference
+ * counterpart; opt-in), the densification signal that does not cancel.  dL_dmean2D is the SIGNED sum over pixels of
+ * each pixel's pull on the 2-D mean (backward.cu:541-546), so a large blurry Gaussian pulled left by half of its
+ * pixels and right by the other half gets ~0 and is never split.  abs_dmean2D (P x 3 floats, device) receives, in
+ * dL_dmean2D's units,
+ *     abs_dmean2D[3 i + 0] = width / 2  * sum_p | dL/dG_p * dG/ddelx_p |
+ *     abs_dmean2D[3 i + 1] = height / 2 * sum_p | dL/dG_p * dG/ddely_p |
+ *     abs_dmean2D[3 i + 2] = 0
+ * over the pixels p where the backward blends Gaussian i (the contributor, 1/255, power > 0 and 0.99-cap rules as in
+ * gs4d_backward_ex; dL/dalpha includes whatever the call back-propagates: colour, and depth / alpha when given).  A
+ * skipped pixel adds an exact 0; a Gaussian without instances or with radii == 0 gets exact zeros; every row is
+ * written.  dL_ddepth and dL_dalpha may each be NULL as in gs4d_backward_aux.  Every other output is bit for bit
+ * what gs4d_backward_ex / _depth / _aux give for the same inputs, and abs_dmean2D is bitwise repeatable (no float
+ * atomics: the sums ride the fixed-order reduction of the other gradients).
+ * Layout note: the 48-byte per-instance gradient record the reverse walk stores (12 floats: nine gradient sums,
+ * float 9 = W3 of the depth gradient, floats 10 and 11 = these two absolute sums) is now full; a further
+ * per-instance value needs a wider record.
+ * Status as gs4d_backward_aux, and GS4D_ERR_ARG for a NULL abs_dmean2D (also when P == 0). */
+int gs4d_backward_absgrad(int P, int D, int M, int R, const float *background, int width, int height,
+                          const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                          float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                          const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                          float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer,
+                          char *image_buffer, const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha,
+                          float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D,
+                          gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
+                          int view_transposed);
+
 /* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.

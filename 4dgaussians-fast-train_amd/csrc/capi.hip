@@ -146,10 +146,6 @@ static uint32_t higher_msb(uint32_t n) {
     return msb;
 }
 
-}  // namespace gs4d
-
-namespace gs4d {
-
 // instances are sorted by tile id only; tile ids need msb(T) bits (rasterizer_impl.cu:301)
 size_t BinningState::required(int L, int T) {
     BinningState b = carve(nullptr, L, T);
@@ -325,92 +321,88 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
 
 }  // extern "C"
 
-// gs4d_backward_ex (DEPTH = false) and gs4d_backward_depth (DEPTH = true): the same orchestration over the
-// colour-only or the depth-gradient instantiations of the three backward stages.  dL_dalpha (gs4d_backward_aux;
-// NULL for none) only changes the start value of the reverse walk's running sum, in either instantiation.
-// ABS (gs4d_backward_absgrad): the absgrad instantiations of the three stages, which also fill abs_dmean2D.
-template <bool DEPTH, bool ABS = false>
-static int backward_impl(int P, int D, int M, int R, const float *background, int width, int height,
-                         const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
-                         float scale_modifier, const float *rotations, const float *cov3D_precomp,
-                         const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
-                         float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
-                         const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
-                         float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
-                         float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc,
-                         void *scratch_ctx, int debug, void *stream_, int view_transposed,
-                         float *abs_dmean2D = nullptr) {
-    hipStream_t stream = (hipStream_t)stream_;
+// One backward call, as the six exported entries hand it to backward_impl: gs4d_backward_absgrad's parameters in
+// their order, then what the entry requires.
+namespace {
+struct BackwardCall {
+    int P, D, M, R;
+    const float *background;
+    int width, height;
+    const float *means3D, *shs, *colors_precomp, *scales;
+    float scale_modifier;
+    const float *rotations, *cov3D_precomp, *viewmatrix, *projmatrix, *campos;
+    float tan_fovx, tan_fovy;
+    const int *radii;
+    char *geom_buffer, *binning_buffer, *image_buffer;
+    const float *dL_dpix, *dL_ddepth, *dL_dalpha;  // the upstream images; NULL dL_ddepth / dL_dalpha: no such gradient
+    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
+    float *abs_dmean2D;  // NULL: no absgrad
+    gs4d_alloc_fn scratch_alloc;
+    void *scratch_ctx;
+    int debug;
+    void *stream;
+    int view_transposed;
+    bool need_depth, need_abs;  // gs4d_backward_depth / gs4d_backward_absgrad: a NULL dL_ddepth / abs_dmean2D is an error
+};
+}  // namespace
+
+// The one orchestration of the three backward stages.  dL_ddepth selects their depth-gradient instantiations and
+// abs_dmean2D their absgrad instantiations (which also fill it); dL_dalpha only changes the start value of the
+// reverse walk's running sum, in every instantiation.
+static int backward_impl(const BackwardCall &c) {
+    hipStream_t stream = (hipStream_t)c.stream;
+    const int debug = c.debug, P = c.P, R = c.R;
     if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "backward: bad sizes");
-    if (ABS && !abs_dmean2D) return fail(GS4D_ERR_ARG, "backward_absgrad: missing abs_dmean2D");
+    if (c.need_abs && !c.abs_dmean2D) return fail(GS4D_ERR_ARG, "backward_absgrad: missing abs_dmean2D");
     if (P == 0) return GS4D_OK;
-    if (DEPTH && (!dL_ddepth || !dL_dpix)) return fail(GS4D_ERR_ARG, "backward_depth: missing dL_ddepth or dL_dpix");
-    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer) || !dL_dpix || !means3D)
+    if (c.need_depth && (!c.dL_ddepth || !c.dL_dpix))
+        return fail(GS4D_ERR_ARG, "backward_depth: missing dL_ddepth or dL_dpix");
+    if (!c.geom_buffer || !c.image_buffer || (R > 0 && !c.binning_buffer) || !c.dL_dpix || !c.means3D)
         return fail(GS4D_ERR_ARG, "backward: missing buffers");
-    if (shs && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
+    if (c.shs && (c.D < 0 || c.D > 3 || (c.D + 1) * (c.D + 1) > c.M))
         return fail(GS4D_ERR_ARG, "backward: SH degree must be in [0,3] with (D+1)^2 <= M coefficients");
-    if (rotations && ((size_t)rotations & 15) != 0) return fail(GS4D_ERR_ARG, "backward: rotations must be 16-byte aligned");
-    if (((size_t)dL_drot & 15) != 0) return fail(GS4D_ERR_ARG, "backward: dL_drot must be 16-byte aligned");
-    if (!viewmatrix || !projmatrix || !background || (shs && !campos))
+    if (c.rotations && ((size_t)c.rotations & 15) != 0)
+        return fail(GS4D_ERR_ARG, "backward: rotations must be 16-byte aligned");
+    if (((size_t)c.dL_drot & 15) != 0) return fail(GS4D_ERR_ARG, "backward: dL_drot must be 16-byte aligned");
+    if (!c.viewmatrix || !c.projmatrix || !c.background || (c.shs && !c.campos))
         return fail(GS4D_ERR_ARG, "backward: missing camera inputs");
-    Args a = make_args(P, D, M, width, height, background, scale_modifier, viewmatrix, projmatrix, campos, tan_fovx,
-                       tan_fovy, 0);
-    a.view_transposed = view_transposed ? 1 : 0;
+    const bool depth = c.dL_ddepth != nullptr;
+    Args a = make_args(P, c.D, c.M, c.width, c.height, c.background, c.scale_modifier, c.viewmatrix, c.projmatrix,
+                       c.campos, c.tan_fovx, c.tan_fovy, 0);
+    a.view_transposed = c.view_transposed ? 1 : 0;
     begin_marks(stream);
     const int T = a.gx * a.gy;
-    GeomState g = GeomState::carve(geom_buffer, P, T);
-    ImageState img = ImageState::carve(image_buffer, width, height);
-    const int *radii_ptr = radii ? radii : g.radii;
+    GeomState g = GeomState::carve(c.geom_buffer, P, T);
+    ImageState img = ImageState::carve(c.image_buffer, c.width, c.height);
+    const int *radii_ptr = c.radii ? c.radii : g.radii;
     // backward scratch: per-instance gradient records (R x 48 B) | per-Gaussian conic gradients |
     // segmented-reduction partials
     const size_t rec_bytes = align_up((size_t)R * kContribStride * sizeof(float), 256);
     const size_t dconic_bytes = align_up(16 * (size_t)P, 256);
-    char *scratch = scratch_alloc(scratch_ctx, rec_bytes + dconic_bytes + contrib_scratch_bytes(R, P) + 256);
+    char *scratch = c.scratch_alloc(c.scratch_ctx, rec_bytes + dconic_bytes + contrib_scratch_bytes(R, P) + 256);
     if (!scratch) return fail(GS4D_ERR_ALLOC, "backward: scratch allocation failed");
     float *contrib = (float *)align_up((size_t)scratch, 256);
     char *reduce_scratch = (char *)contrib + rec_bytes + dconic_bytes;
-    float4 *dconic = (dL_dconic && ((size_t)dL_dconic & 15) == 0) ? (float4 *)dL_dconic
-                                                                   : (float4 *)((char *)contrib + rec_bytes);
+    float4 *dconic = (c.dL_dconic && ((size_t)c.dL_dconic & 15) == 0) ? (float4 *)c.dL_dconic
+                                                                       : (float4 *)((char *)contrib + rec_bytes);
     BinningState b = {};
     if (R > 0) {
-        b = BinningState::carve(binning_buffer, R, T);
-        const float *color_ptr = colors_precomp;  // NULL -> the forward's rgb (rasterizer_impl.cu:392)
-        if (ABS)
-            GS4D_REPEATED_STAGE("render_backward", launch_render_backward_abs(a, g, b.gid_by_e, b.upos, img, dL_dpix,
-                                                                              DEPTH ? dL_ddepth : nullptr, dL_dalpha,
-                                                                              contrib, stream));
-        else if (DEPTH)
-            GS4D_REPEATED_STAGE("render_backward", launch_render_backward_depth(a, g, b.gid_by_e, b.upos, img, dL_dpix,
-                                                                                dL_ddepth, dL_dalpha, contrib, stream));
-        else
-            GS4D_REPEATED_STAGE("render_backward", launch_render_backward(a, g, b.gid_by_e, b.upos, img, color_ptr,
-                                                                          dL_dpix, dL_dalpha, contrib, stream));
+        b = BinningState::carve(c.binning_buffer, R, T);
+        // the blend reads the colours from the forward's splat records (rasterizer_impl.cu:392)
+        GS4D_REPEATED_STAGE("render_backward",
+                            launch_render_backward(a, g, b.gid_by_e, b.upos, img, c.dL_dpix, c.dL_ddepth, c.dL_dalpha,
+                                                   c.abs_dmean2D != nullptr, contrib, stream));
     }
-    const float *cov3D_ptr = cov3D_precomp ? cov3D_precomp : g.cov3D;  // rasterizer_impl.cu:414
-    if (ABS) {
-        GS4D_STAGE("contrib_reduce", launch_contrib_reduce_abs(a, g, b, R, contrib, reduce_scratch, DEPTH, dL_dmean2D,
-                                                               dconic, dL_dopacity, dL_dcolor, abs_dmean2D, stream));
-        GS4D_STAGE("gaussian_backward",
-                   launch_gaussian_backward_abs(a, g, R, reduce_scratch, DEPTH, radii_ptr, means3D, shs, scales,
-                                                rotations, cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dL_dcolor,
-                                                dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, abs_dmean2D, stream));
-    } else if (DEPTH) {
-        GS4D_STAGE("contrib_reduce", launch_contrib_reduce_depth(a, g, b, R, contrib, reduce_scratch, dL_dmean2D, dconic,
-                                                                 dL_dopacity, dL_dcolor, stream));
-        GS4D_STAGE("gaussian_backward",
-                   launch_gaussian_backward_depth(a, g, R, reduce_scratch, radii_ptr, means3D, shs, scales, rotations,
-                                                  cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                                                  dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream));
-    } else {
-        GS4D_STAGE("contrib_reduce", launch_contrib_reduce(a, g, b, R, contrib, reduce_scratch, dL_dmean2D, dconic,
-                                                           dL_dopacity, dL_dcolor, stream));
-        GS4D_STAGE("gaussian_backward",
-                   launch_gaussian_backward(a, g, R, reduce_scratch, radii_ptr, means3D, shs, scales, rotations,
-                                            cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                                            dL_dcov3D, dL_dsh, dL_dscale, dL_drot, stream));
-    }
-    if (dL_dconic && (float *)dconic != dL_dconic)
-        GS4D_HIP(hipMemcpyAsync(dL_dconic, dconic, 16 * (size_t)P, hipMemcpyDeviceToDevice, stream));
+    const float *cov3D_ptr = c.cov3D_precomp ? c.cov3D_precomp : g.cov3D;  // rasterizer_impl.cu:414
+    GS4D_STAGE("contrib_reduce", launch_contrib_reduce(a, g, b, R, contrib, reduce_scratch, depth, c.dL_dmean2D, dconic,
+                                                       c.dL_dopacity, c.dL_dcolor, c.abs_dmean2D, stream));
+    GS4D_STAGE("gaussian_backward",
+               launch_gaussian_backward(a, g, R, reduce_scratch, depth, radii_ptr, c.means3D, c.shs, c.scales,
+                                        c.rotations, cov3D_ptr, c.dL_dmean2D, dconic, c.dL_dopacity, c.dL_dcolor,
+                                        c.dL_dmean3D, c.dL_dcov3D, c.dL_dsh, c.dL_dscale, c.dL_drot, c.abs_dmean2D,
+                                        stream));
+    if (c.dL_dconic && (float *)dconic != c.dL_dconic)
+        GS4D_HIP(hipMemcpyAsync(c.dL_dconic, dconic, 16 * (size_t)P, hipMemcpyDeviceToDevice, stream));
     end_marks();
     return GS4D_OK;
 }
@@ -426,11 +418,11 @@ int gs4d_backward_ex(int P, int D, int M, int R, const float *background, int wi
                      float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
                      float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
                      int view_transposed) {
-    return backward_impl<false>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, nullptr,
-                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, nullptr, dL_dmean2D, dL_dconic,
+                          dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr,
+                          scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, false});
 }
 
 int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int width, int height,
@@ -442,11 +434,11 @@ int gs4d_backward_depth(int P, int D, int M, int R, const float *background, int
                         float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
                         float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug,
                         void *stream, int view_transposed) {
-    return backward_impl<true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                               tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, nullptr,
-                               dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                               dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, nullptr, dL_dmean2D, dL_dconic,
+                          dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr,
+                          scratch_alloc, scratch_ctx, debug, stream, view_transposed, true, false});
 }
 
 int gs4d_backward_aux(int P, int D, int M, int R, const float *background, int width, int height,
@@ -458,18 +450,11 @@ int gs4d_backward_aux(int P, int D, int M, int R, const float *background, int w
                       float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
                       float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
                       int debug, void *stream, int view_transposed) {
-    if (dL_ddepth)
-        return backward_impl<true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                   tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth,
-                                   dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                   dL_dscale, dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
-    // no depth gradient: the colour-only instantiations of the three stages
-    return backward_impl<false>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, dL_dalpha,
-                                dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                dL_drot, scratch_alloc, scratch_ctx, debug, stream, view_transposed);
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dalpha, dL_dmean2D,
+                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr,
+                          scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, false});
 }
 
 int gs4d_backward_absgrad(int P, int D, int M, int R, const float *background, int width, int height,
@@ -482,19 +467,11 @@ int gs4d_backward_absgrad(int P, int D, int M, int R, const float *background, i
                           float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D,
                           gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
                           int view_transposed) {
-    if (dL_ddepth)
-        return backward_impl<true, true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
-                                         tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                         dL_ddepth, dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch_alloc, scratch_ctx, debug,
-                                         stream, view_transposed, abs_dmean2D);
-    return backward_impl<false, true>(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                                      scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
-                                      tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                      nullptr, dL_dalpha, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                                      dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch_alloc, scratch_ctx, debug, stream,
-                                      view_transposed, abs_dmean2D);
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dalpha, dL_dmean2D,
+                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                          abs_dmean2D, scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, true});
 }
 
 int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out_alpha, void *stream) {
@@ -527,11 +504,11 @@ int gs4d_backward(int P, int D, int M, int R, const float *background, int width
                   float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                   float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc,
                   void *scratch_ctx, int debug, void *stream) {
-    return gs4d_backward_ex(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                            scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                            tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
-                            dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                            scratch_alloc, scratch_ctx, debug, stream, 0);
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, nullptr, nullptr, dL_dmean2D, dL_dconic,
+                          dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr,
+                          scratch_alloc, scratch_ctx, debug, stream, 0, false, false});
 }
 
 int gs4d_knn_mean_dist(int P, const float *points, float *mean_dists, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gs4d_math.h"
 
 namespace gs4d {
@@ -200,51 +202,36 @@ hipError_t launch_render_forward(const Args &a, GeomState g, BinningState b, Ima
                                  float *out_depth, hipStream_t s);  // also sorts runs <= kWaveSortMax
 hipError_t launch_pair_alpha(GeomState g, int n, const int *gid, const int *px, const int *py, float *og, float *pw,
                              hipStream_t s);
-hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos, ImageState img,
-                                  const float *colors, const float *dL_dpix, const float *dL_dalpha, float *contrib,
-                                  hipStream_t s);
-// the depth-gradient backward (gs4d_backward_depth): the same three stages with dL/ddepth; the records' float 9
-// carries W3 = sum w dL/ddepth, whose per-Gaussian sum travels in dL_dconic's unused .z slot
-// dL_dalpha (both walks; NULL for none): the gradient of the alpha image 1 - T_final (gs4d_backward_aux)
-hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                        ImageState img, const float *dL_dpix, const float *dL_ddepth,
-                                        const float *dL_dalpha, float *contrib, hipStream_t s);
-// out_alpha[pix] = 1 - final_T[pix] over the n = W * H pixels of the forward's image state (gs4d_alpha_image)
-hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStream_t s);
-hipError_t launch_contrib_reduce_depth(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
-                                       char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                       float *dL_dcolor, hipStream_t s);
-hipError_t launch_gaussian_backward_depth(const Args &a, GeomState g, int R, char *scratch, const int *radii,
-                                          const float *means3D, const float *shs, const float *scales,
-                                          const float *rotations, const float *cov3D, float *dL_dmean2D,
-                                          float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                          hipStream_t s);
-// the absgrad backward (gs4d_backward_absgrad): the three stages carrying the records' floats 10 and 11 (sums over
-// pixels of |per-pixel mean2D term|) into abs_dmean2D (P x 3); dL_ddepth != NULL / depth selects the W3 variants
-hipError_t launch_render_backward_abs(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                      ImageState img, const float *dL_dpix, const float *dL_ddepth,
-                                      const float *dL_dalpha, float *contrib, hipStream_t s);
-hipError_t launch_contrib_reduce_abs(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
-                                     char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
-                                     float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s);
-hipError_t launch_gaussian_backward_abs(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
-                                        const float *means3D, const float *shs, const float *scales,
-                                        const float *rotations, const float *cov3D, float *dL_dmean2D,
-                                        float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                                        float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                        float *abs_dmean2D, hipStream_t s);
+// The backward's three stages, one launcher each over the kernels' <DEPTH / NV, ABS> instantiations.
+// depth (dL_ddepth != NULL at the blend): the depth-gradient walk (gs4d_backward_depth); the records' float 9
+// carries W3 = sum w dL/ddepth, whose per-Gaussian sum travels in dL_dconic's unused .z slot.
+// abs (abs_dmean2D != NULL after the blend): the absgrad walk (gs4d_backward_absgrad); the records' floats 10 and
+// 11 (sums over pixels of |per-pixel mean2D term|) end in abs_dmean2D (P x 3).
+// dL_dalpha (every walk; NULL for none): the gradient of the alpha image 1 - T_final (gs4d_backward_aux).
+hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
+                                  ImageState img, const float *dL_dpix, const float *dL_ddepth,
+                                  const float *dL_dalpha, bool abs, float *contrib, hipStream_t s);
 size_t contrib_scratch_bytes(int R, int P);
 hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
-                                 char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                 float *dL_dcolor, hipStream_t s);
+                                 char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
+                                 float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s);
 // also finishes the contrib_reduce sums of Gaussians spanning waves (same scratch) and zero-fills the
 // render-level gradients of Gaussians without instances
-hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
-                                    const float *means3D, const float *shs, const float *scales, const float *rotations,
-                                    const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                    float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
-                                    float *dL_dscale, float *dL_drot, hipStream_t s);
+hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
+                                    const float *means3D, const float *shs, const float *scales,
+                                    const float *rotations, const float *cov3D, float *dL_dmean2D,
+                                    float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                                    float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
+                                    float *abs_dmean2D, hipStream_t s);
+// The two run-time flags as compile-time constants: f(std::bool_constant<depth>{}, std::bool_constant<abs>{}),
+// for the launchers' choice among a kernel's four instantiations.
+template <class F>
+hipError_t with_backward_variant(bool depth, bool abs, F &&f) {
+    if (depth) return abs ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return abs ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+// out_alpha[pix] = 1 - final_T[pix] over the n = W * H pixels of the forward's image state (gs4d_alpha_image)
+hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStream_t s);
 
 size_t knn_scratch_bytes(int P);
 hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch, hipStream_t s);

@@ -354,7 +354,7 @@ size_t contrib_scratch_bytes(int R, int P) {
 }
 
 static GradOut grad_out(const Args &a, GeomState g, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                        float *dL_dcolor, float *abs_dmean2D = nullptr) {
+                        float *dL_dcolor, float *abs_dmean2D) {
     return GradOut{dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, g.conic_opacity, 0.5f * a.W, 0.5f * a.H, abs_dmean2D};
 }
 static float4 *scratch_part(char *scratch) { return (float4 *)scratch; }
@@ -363,10 +363,10 @@ static uint32_t *scratch_e_first(char *scratch, int R) {
     return (uint32_t *)(scratch + align_up(nw * 2 * 3 * sizeof(float4), 256));
 }
 
-template <int NV, bool ABS = false>
+template <int NV, bool ABS>
 static hipError_t contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                 float *dL_dcolor, hipStream_t s, float *abs_dmean2D = nullptr) {
+                                 float *dL_dcolor, float *abs_dmean2D, hipStream_t s) {
     if (R == 0) return hipSuccess;  // every Gaussian has n_inst = 0: gaussian_backward writes the zeros
     const size_t nw = ((size_t)R + 63) / 64;
     const uint32_t *n_dev = b.scratch;  // L' (binning.hip)
@@ -377,23 +377,12 @@ static hipError_t contrib_reduce(const Args &a, GeomState g, BinningState b, int
     return hipGetLastError();
 }
 
-hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
-                                 char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                 float *dL_dcolor, hipStream_t s) {
-    return contrib_reduce<9>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s);
-}
-hipError_t launch_contrib_reduce_depth(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
-                                       char *scratch, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                       float *dL_dcolor, hipStream_t s) {
-    return contrib_reduce<10>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s);
-}
-
-template <int NV, bool ABS = false>
+template <int NV, bool ABS>
 static hipError_t gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
                                     const float *means3D, const float *shs, const float *scales, const float *rotations,
                                     const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
                                     float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
-                                    float *dL_dscale, float *dL_drot, hipStream_t s, float *abs_dmean2D = nullptr) {
+                                    float *dL_dscale, float *dL_drot, float *abs_dmean2D, hipStream_t s) {
     const GradOut o = grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, abs_dmean2D);
     if (shs) {
         const bool vec4 = a.M == 16 && (((size_t)shs | (size_t)dL_dsh) & 15) == 0;
@@ -409,48 +398,28 @@ static hipError_t gaussian_backward(const Args &a, GeomState g, int R, char *scr
     }
     return hipGetLastError();
 }
-hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
-                                    const float *means3D, const float *shs, const float *scales, const float *rotations,
-                                    const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
-                                    float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
-                                    float *dL_dscale, float *dL_drot, hipStream_t s) {
-    return gaussian_backward<9>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic,
-                                dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, s);
-}
-hipError_t launch_gaussian_backward_depth(const Args &a, GeomState g, int R, char *scratch, const int *radii,
-                                          const float *means3D, const float *shs, const float *scales,
-                                          const float *rotations, const float *cov3D, float *dL_dmean2D,
-                                          float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                                          float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                          hipStream_t s) {
-    return gaussian_backward<10>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic,
-                                 dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, s);
-}
 
-// the absgrad backward (gs4d_backward_absgrad): the same two stages carrying the records' floats 10 and 11 into
-// abs_dmean2D (P x 3); `depth` selects the instantiations that also carry W3
-hipError_t launch_contrib_reduce_abs(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
-                                     char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
-                                     float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s) {
-    if (depth)
-        return contrib_reduce<10, true>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s,
-                                        abs_dmean2D);
-    return contrib_reduce<9, true>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, s,
-                                   abs_dmean2D);
+// `depth`: the records carry W3 (NV = 10 floats are reduced instead of 9); abs_dmean2D (P x 3, or NULL for none):
+// the absgrad variants, which carry the records' floats 10 and 11 into it
+hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
+                                 char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
+                                 float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s) {
+    return with_backward_variant(depth, abs_dmean2D != nullptr, [&](auto depth_c, auto abs_c) {
+        return contrib_reduce<depth_c.value ? 10 : 9, abs_c.value>(a, g, b, R, contrib, scratch, dL_dmean2D, dL_dconic,
+                                                                   dL_dopacity, dL_dcolor, abs_dmean2D, s);
+    });
 }
-hipError_t launch_gaussian_backward_abs(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
-                                        const float *means3D, const float *shs, const float *scales,
-                                        const float *rotations, const float *cov3D, float *dL_dmean2D,
-                                        float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
-                                        float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                        float *abs_dmean2D, hipStream_t s) {
-    if (depth)
-        return gaussian_backward<10, true>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
-                                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                           dL_drot, s, abs_dmean2D);
-    return gaussian_backward<9, true>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
-                                      dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                      dL_drot, s, abs_dmean2D);
+hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
+                                    const float *means3D, const float *shs, const float *scales,
+                                    const float *rotations, const float *cov3D, float *dL_dmean2D,
+                                    float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                                    float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
+                                    float *abs_dmean2D, hipStream_t s) {
+    return with_backward_variant(depth, abs_dmean2D != nullptr, [&](auto depth_c, auto abs_c) {
+        return gaussian_backward<depth_c.value ? 10 : 9, abs_c.value>(
+            a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dopacity,
+            dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, abs_dmean2D, s);
+    });
 }
 
 }  // namespace gs4d

@@ -579,16 +579,8 @@ struct BwdPixels {
     f2 T[2], A[2], dp0[2], dp1[2], dp2[2], dd[2];
 };
 
-// One half tile of one splat of the reverse walk: updates the half's pixel state and adds its
-// per-lane partial sums (moments of u' = o G dL/dalpha in the tile-centred row coordinate yl -- the
-// record divides them by o once -- and the colour sums) to U0..U2 / W0..W2.  The falloff is the
-// forward's sequence (falloff()) on operand pairs: identical blend decisions.  Branch-free, so that the
-// pair walk below is one basic block.
-//   ALL: the splat lies below every pixel's n_contrib (the contributor test passes; pixels outside
-//        the image have T = dL/dpix = 0 and contribute exact zeros).
-//   GEN: the general splat: `chk` = its conic is not positive definite (power > 0 skips, forward.cu:341),
-//        and the 0.99 cap applies; without GEN the opacity is <= kCapFree, so o * G never reaches the cap.
-// The per-splat half of a step: falloff, the reference's skip decisions and alpha.
+// The per-splat half of a step (half_step below, which explains ALL and GEN): falloff, the reference's skip
+// decisions and alpha.
 struct HalfAlpha {
     f2 ale, ae, om;  // o G with the skips applied, alpha, 1 - alpha
     f2 dy;           // mean row - pixel row (read by the absgrad walk only)
@@ -953,39 +945,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_waves(DE
     }
 }
 
-// dL_dalpha (H x W, or NULL for none): the alpha image's gradient (gs4d_backward_aux)
+// dL_ddepth (H x W, or NULL for none) selects the walk with dL/ddepth, whose records also carry W3 in float 9; abs
+// the absgrad walk, whose records also carry the absolute sums in floats 10 and 11; dL_dalpha (H x W, or NULL for
+// none): the alpha image's gradient.  The splat records hold the colours the forward blended (colors_precomp or SH).
 hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                  ImageState img, const float *colors, const float *dL_dpix, const float *dL_dalpha,
-                                  float *contrib, hipStream_t s) {
+                                  ImageState img, const float *dL_dpix, const float *dL_ddepth,
+                                  const float *dL_dalpha, bool abs, float *contrib, hipStream_t s) {
     const int T = a.gx * a.gy;
-    (void)colors;  // the splat records hold the colours the forward blended (colors_precomp or SH)
-    hipLaunchKernelGGL((render_backward_kernel<false, false>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
-                       gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, dL_dalpha, contrib);
-    return hipGetLastError();
-}
-// the same walk with dL/ddepth (H x W): every record also carries W3 in float 9
-hipError_t launch_render_backward_depth(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                        ImageState img, const float *dL_dpix, const float *dL_ddepth,
-                                        const float *dL_dalpha, float *contrib, hipStream_t s) {
-    const int T = a.gx * a.gy;
-    hipLaunchKernelGGL((render_backward_kernel<true, false>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
-                       gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha, contrib);
-    return hipGetLastError();
-}
-
-// the absgrad walk (gs4d_backward_absgrad): every record also carries the absolute sums in floats 10 and 11;
-// dL_ddepth (NULL for none) selects the depth instantiation
-hipError_t launch_render_backward_abs(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
-                                      ImageState img, const float *dL_dpix, const float *dL_ddepth,
-                                      const float *dL_dalpha, float *contrib, hipStream_t s) {
-    const int T = a.gx * a.gy;
-    if (dL_ddepth)
-        hipLaunchKernelGGL((render_backward_kernel<true, true>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
-                           gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha, contrib);
-    else
-        hipLaunchKernelGGL((render_backward_kernel<false, true>), dim3(T), dim3(64), 0, s, a, img.ranges, img.order,
-                           gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, nullptr, dL_dalpha, contrib);
-    return hipGetLastError();
+    return with_backward_variant(dL_ddepth != nullptr, abs, [&](auto depth_c, auto abs_c) {
+        hipLaunchKernelGGL((render_backward_kernel<depth_c.value, abs_c.value>), dim3(T), dim3(64), 0, s, a, img.ranges,
+                           img.order, gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha,
+                           contrib);
+        return hipGetLastError();
+    });
 }
 
 // gs4d_alpha_image: the accumulated alpha A = sum alpha_i T_i = 1 - T_final of every pixel, from the final_T the

@@ -182,42 +182,29 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
         char *binning = binningBuffer.numel() ? reinterpret_cast<char *>(binningBuffer.data_ptr()) : nullptr;
         char *image = reinterpret_cast<char *>(imageBuffer.data_ptr());
         float *dsh = M ? dL_dsh.data_ptr<float>() : nullptr;
-        int st;
+        // every entry takes the same 23 inputs, then its upstream images, the nine gradient outputs (dL_dconic is not
+        // wanted), abs_dmean2D where it has one, and the same tail
+        const auto head = std::make_tuple(P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc),
+                                          scale_modifier, fptr(rot), fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx,
+                                          tan_fovy, rad_ptr, geom, binning, image);
+        const auto outs = std::make_tuple(dL_dmeans2D.data_ptr<float>(), (float *)nullptr, dL_dopacity.data_ptr<float>(),
+                                          dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
+                                          dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(),
+                                          dL_drotations.data_ptr<float>());
+        const auto tail = std::make_tuple(&resize_cb, (void *)&rs, debug ? 1 : 0, (void *)stream, vt);
+        const float *pix = fptr(dl), *dep = dd.defined() ? fptr(dd) : nullptr, *alp = da.defined() ? fptr(da) : nullptr;
+        const auto call = [&](const char *what, auto entry, auto images, auto abs_ptr) {
+            check_status(std::apply(entry, std::tuple_cat(head, images, outs, abs_ptr, tail)), what);
+        };
         if (abs_out)
-            st = gs4d_backward_absgrad(
-                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
-                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
-                dd.defined() ? fptr(dd) : nullptr, da.defined() ? fptr(da) : nullptr, dL_dmeans2D.data_ptr<float>(),
-                nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
-                dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
-                abs_out->data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
+            call("rasterize_gaussians_backward_absgrad", gs4d_backward_absgrad, std::make_tuple(pix, dep, alp),
+                 std::make_tuple(abs_out->data_ptr<float>()));
         else if (dL_dout_alpha)
-            st = gs4d_backward_aux(
-                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
-                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
-                dd.defined() ? fptr(dd) : nullptr, da.defined() ? fptr(da) : nullptr, dL_dmeans2D.data_ptr<float>(),
-                nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(),
-                dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(),
-                resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
+            call("rasterize_gaussians_backward_aux", gs4d_backward_aux, std::make_tuple(pix, dep, alp), std::tuple<>());
         else if (dL_dout_depth)
-            st = gs4d_backward_depth(
-                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
-                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
-                fptr(dd), dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(),
-                dL_dcolors.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), dsh,
-                dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0,
-                (void *)stream, vt);
+            call("rasterize_gaussians_backward_depth", gs4d_backward_depth, std::make_tuple(pix, dep), std::tuple<>());
         else
-            st = gs4d_backward_ex(
-                P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier, fptr(rot),
-                fptr(c3), fptr(vm), fptr(pm), fptr(cp), tan_fovx, tan_fovy, rad_ptr, geom, binning, image, fptr(dl),
-                dL_dmeans2D.data_ptr<float>(), nullptr, dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
-                dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(), dsh, dL_dscales.data_ptr<float>(),
-                dL_drotations.data_ptr<float>(), resize_cb, &rs, debug ? 1 : 0, (void *)stream, vt);
-        check_status(st, abs_out         ? "rasterize_gaussians_backward_absgrad"
-                         : dL_dout_alpha ? "rasterize_gaussians_backward_aux"
-                         : dL_dout_depth ? "rasterize_gaussians_backward_depth"
-                                         : "rasterize_gaussians_backward");
+            call("rasterize_gaussians_backward", gs4d_backward_ex, std::make_tuple(pix), std::tuple<>());
     }
     return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
                            dL_drotations);

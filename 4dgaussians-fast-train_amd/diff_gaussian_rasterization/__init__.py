@@ -69,216 +69,140 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     """(color, radii, depth), or with alpha=True (color, radii, depth, alpha).  absgrad=True: the backward also
     assigns `means2D.absgrad` (P, 3): per Gaussian the sum over its pixels of |the pixel's term of means2D.grad|
     in x and y (column 2 is 0), where means2D.grad holds the signed sum."""
-    if absgrad:
-        if alpha:
-            fn = _RasterizeGaussiansAuxDepthAbs if depth_grad else _RasterizeGaussiansAuxAbs
-        else:
-            fn = _RasterizeGaussiansAbsDepth if depth_grad else _RasterizeGaussiansAbs
-    elif alpha:
-        fn = _RasterizeGaussiansAuxDepth if depth_grad else _RasterizeGaussiansAux
-    else:
-        fn = _RasterizeGaussiansDepth if depth_grad else _RasterizeGaussians
+    fn = _FUNCTIONS[bool(depth_grad), bool(alpha), bool(absgrad)]
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                     raster_settings)
 
 
-class _RasterizeGaussians(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
-        s = raster_settings
-        # positional order of _C.rasterize_gaussians (rasterize_points.h:18-38)
-        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug)
-        num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
-            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        # radii are integers and the depth image gets no gradient (below): autograd need not build
-        # zero gradients for them before calling backward
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf,
-                              binning_buf, img_buf)
-        return color, radii, depth
+def _zero_image(channels, s, like):
+    return torch.zeros((channels, s.image_height, s.image_width), dtype=torch.float32, device=like.device)
 
-    @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth):
-        # grad_radii and grad_depth are ignored, exactly like the reference (:100-101): no gradient
-        # flows from the depth image.
-        s = ctx.raster_settings
-        if grad_out_color is None:  # only the depth image was used: nothing flows back (as the reference)
-            return (None,) * 9
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
-         img_buf) = ctx.saved_tensors
-        # positional order of _C.rasterize_gaussians_backward (rasterize_points.h:40-62)
-        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, sh, s.sh_degree, s.campos,
-                geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
-        (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _invoke(
-            _C.rasterize_gaussians_backward, args, s.debug, "snapshot_bw.dump", "backward")
-        return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+
+def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+             raster_settings):
+    depth_grad, alpha, absgrad = variant
+    s = raster_settings
+    # positional order of _C.rasterize_gaussians (rasterize_points.h:18-38)
+    args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
+            s.campos, s.prefiltered, s.debug)
+    num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
+        _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
+    ctx.variant = variant
+    ctx.raster_settings = s
+    ctx.num_rendered = num_rendered
+    # radii are integers, and a gradient that did not arrive means "none" to the backward: autograd need not
+    # build zero gradients before calling it
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf,
+                          binning_buf, img_buf)
+    if absgrad:
+        ctx.absgrad_target = means2D  # the caller's tensor: the backward assigns its .absgrad
+    if not alpha:
+        return color, radii, depth
+    if means3D.shape[0] == 0:  # nothing was drawn and there is no image state to read
+        alpha_image = _zero_image(1, s, means3D)
+    else:
+        alpha_image = _C.alpha_image(img_buf, s.image_height, s.image_width)
+    return color, radii, depth, alpha_image
+
+
+def _backward(ctx, grad_out_color, grad_depth, grad_alpha):
+    depth_grad, alpha, absgrad = ctx.variant
+    s = ctx.raster_settings
+    if not depth_grad:  # no gradient flows from the depth image, exactly like the reference (:100-101)
+        grad_depth = None
+    if grad_out_color is None and grad_depth is None and grad_alpha is None:
+        return (None,) * 9  # only images without a gradient path were used: nothing flows back
+    (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
+     img_buf) = ctx.saved_tensors
+    # the entry and its upstream images, which follow grad_out_color in its argument list
+    if alpha or absgrad:  # an empty tensor stands for "no such gradient"
+        entry = _C.rasterize_gaussians_backward_absgrad if absgrad else _C.rasterize_gaussians_backward_aux
+        if grad_out_color is None:
+            grad_out_color = _zero_image(3, s, means3D)
+        none = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        grads = (grad_out_color, none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha)
+    elif depth_grad:
+        entry = _C.rasterize_gaussians_backward_depth
+        if grad_out_color is None:
+            grad_out_color = _zero_image(3, s, means3D)
+        if grad_depth is None:
+            grad_depth = _zero_image(1, s, means3D)
+        grads = (grad_out_color, grad_depth)
+    else:
+        entry = _C.rasterize_gaussians_backward
+        grads = (grad_out_color,)
+    # positional order of _C.rasterize_gaussians_backward (rasterize_points.h:40-62)
+    args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, *grads, sh, s.sh_degree, s.campos,
+            geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
+    out = _invoke(entry, args, s.debug, "snapshot_bw.dump", "backward")
+    if absgrad:
+        ctx.absgrad_target.absgrad = out[8]  # overwritten per backward call (gsplat's convention)
+    g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations = out[:8]
+    return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+
+
+def _variant(depth_grad, alpha, absgrad):
+    """(forward, backward) of the Function with these options, over the shared bodies above."""
+    variant = (depth_grad, alpha, absgrad)
+
+    def forward(ctx, *inputs):
+        return _forward(ctx, variant, *inputs)
+
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
+        return _backward(ctx, grad_out_color, grad_depth, grad_alpha)
+
+    return staticmethod(forward), staticmethod(backward)
+
+
+class _RasterizeGaussians(torch.autograd.Function):
+    forward, backward = _variant(False, False, False)
 
 
 class _RasterizeGaussiansDepth(torch.autograd.Function):
     """_RasterizeGaussians whose backward also takes the depth image's gradient (opt-in: depth_grad=True)."""
-
-    forward = staticmethod(_RasterizeGaussians.forward)  # identical: same launches, same saved tensors
-
-    @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth):
-        s = ctx.raster_settings
-        if grad_out_color is None and grad_depth is None:
-            return (None,) * 9
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
-         img_buf) = ctx.saved_tensors
-        H, W = s.image_height, s.image_width
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((3, H, W), dtype=torch.float32, device=means3D.device)
-        if grad_depth is None:
-            grad_depth = torch.zeros((1, H, W), dtype=torch.float32, device=means3D.device)
-        # _C.rasterize_gaussians_backward's positional order with grad_depth after grad_out_color
-        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, grad_depth, sh, s.sh_degree,
-                s.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
-        (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _invoke(
-            _C.rasterize_gaussians_backward_depth, args, s.debug, "snapshot_bw.dump", "backward")
-        return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+    forward, backward = _variant(True, False, False)
 
 
 class _RasterizeGaussiansAux(torch.autograd.Function):
     """_RasterizeGaussians that also returns the alpha image 1 - T_final (opt-in: alpha=True), whose gradient flows
     back through _C.rasterize_gaussians_backward_aux; the depth image's gradient is dropped, as by default."""
-
-    @staticmethod
-    def forward(ctx, *inputs):
-        return _aux_forward(ctx, False, *inputs)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha):
-        return _aux_backward(ctx, grad_out_color, grad_depth, grad_alpha)
+    forward, backward = _variant(False, True, False)
 
 
 class _RasterizeGaussiansAuxDepth(torch.autograd.Function):
     """_RasterizeGaussiansAux whose backward takes the depth image's gradient too (alpha=True, depth_grad=True)."""
-
-    @staticmethod
-    def forward(ctx, *inputs):
-        return _aux_forward(ctx, True, *inputs)
-
-    backward = staticmethod(_RasterizeGaussiansAux.backward)
-
-
-def _aux_forward(ctx, depth_grad, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                 raster_settings):
-    # the same _C.rasterize_gaussians call and saved tensors as _RasterizeGaussians.forward, then the alpha image
-    color, radii, depth = _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
-                                                      rotations, cov3Ds_precomp, raster_settings)
-    ctx.depth_grad = depth_grad
-    s = raster_settings
-    img_buf = ctx.to_save[-1]  # the forward's image state (save_for_backward's last tensor)
-    if means3D.shape[0] == 0:  # nothing was drawn and there is no image state to read
-        alpha = torch.zeros((1, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
-    else:
-        alpha = _C.alpha_image(img_buf, s.image_height, s.image_width)
-    return color, radii, depth, alpha
-
-
-def _aux_backward(ctx, grad_out_color, grad_depth, grad_alpha):
-    s = ctx.raster_settings
-    if not ctx.depth_grad:
-        grad_depth = None
-    if grad_out_color is None and grad_depth is None and grad_alpha is None:
-        return (None,) * 9
-    (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
-     img_buf) = ctx.saved_tensors
-    if grad_out_color is None:
-        grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
-    none = torch.empty(0, dtype=torch.float32, device=means3D.device)  # "no such gradient"
-    # _C.rasterize_gaussians_backward_depth's positional order with grad_alpha after grad_depth
-    args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color,
-            none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha, sh, s.sh_degree,
-            s.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
-    (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations) = _invoke(
-        _C.rasterize_gaussians_backward_aux, args, s.debug, "snapshot_bw.dump", "backward")
-    return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+    forward, backward = _variant(True, True, False)
 
 
 class _RasterizeGaussiansAbs(torch.autograd.Function):
     """_RasterizeGaussians whose backward also assigns means2D.absgrad (opt-in: absgrad=True)."""
-
-    @staticmethod
-    def forward(ctx, *inputs):
-        return _abs_forward(ctx, False, False, *inputs)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
-        return _abs_backward(ctx, grad_out_color, grad_depth, grad_alpha)
+    forward, backward = _variant(False, False, True)
 
 
 class _RasterizeGaussiansAbsDepth(torch.autograd.Function):
     """_RasterizeGaussiansDepth with means2D.absgrad (absgrad=True, depth_grad=True)."""
-
-    @staticmethod
-    def forward(ctx, *inputs):
-        return _abs_forward(ctx, True, False, *inputs)
-
-    backward = staticmethod(_RasterizeGaussiansAbs.backward)
+    forward, backward = _variant(True, False, True)
 
 
 class _RasterizeGaussiansAuxAbs(torch.autograd.Function):
     """_RasterizeGaussiansAux with means2D.absgrad (absgrad=True, alpha=True)."""
-
-    @staticmethod
-    def forward(ctx, *inputs):
-        return _abs_forward(ctx, False, True, *inputs)
-
-    backward = staticmethod(_RasterizeGaussiansAbs.backward)
+    forward, backward = _variant(False, True, True)
 
 
 class _RasterizeGaussiansAuxDepthAbs(torch.autograd.Function):
     """_RasterizeGaussiansAuxDepth with means2D.absgrad (absgrad=True, alpha=True, depth_grad=True)."""
-
-    @staticmethod
-    def forward(ctx, *inputs):
-        return _abs_forward(ctx, True, True, *inputs)
-
-    backward = staticmethod(_RasterizeGaussiansAbs.backward)
+    forward, backward = _variant(True, True, True)
 
 
-def _abs_forward(ctx, depth_grad, alpha, means3D, means2D, *rest):
-    # the forwards of the Functions without absgrad: the same launches and saved tensors
-    if alpha:
-        out = _aux_forward(ctx, depth_grad, means3D, means2D, *rest)
-    else:
-        out = _RasterizeGaussians.forward(ctx, means3D, means2D, *rest)
-        ctx.depth_grad = depth_grad
-    ctx.absgrad_target = means2D  # the caller's tensor: the backward assigns its .absgrad
-    return out
-
-
-def _abs_backward(ctx, grad_out_color, grad_depth, grad_alpha):
-    s = ctx.raster_settings
-    if not ctx.depth_grad:
-        grad_depth = None
-    if grad_out_color is None and grad_depth is None and grad_alpha is None:
-        return (None,) * 9
-    (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
-     img_buf) = ctx.saved_tensors
-    if grad_out_color is None:
-        grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=torch.float32, device=means3D.device)
-    none = torch.empty(0, dtype=torch.float32, device=means3D.device)  # "no such gradient"
-    # _C.rasterize_gaussians_backward_aux's positional order; one more tensor comes back
-    args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color,
-            none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha, sh, s.sh_degree,
-            s.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
-    (g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations, absgrad) = _invoke(
-        _C.rasterize_gaussians_backward_absgrad, args, s.debug, "snapshot_bw.dump", "backward")
-    ctx.absgrad_target.absgrad = absgrad  # overwritten per backward call (gsplat's convention)
-    return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+# (depth_grad, alpha, absgrad) -> the Function rasterize_gaussians applies
+_FUNCTIONS = {(False, False, False): _RasterizeGaussians, (True, False, False): _RasterizeGaussiansDepth,
+              (False, True, False): _RasterizeGaussiansAux, (True, True, False): _RasterizeGaussiansAuxDepth,
+              (False, False, True): _RasterizeGaussiansAbs, (True, False, True): _RasterizeGaussiansAbsDepth,
+              (False, True, True): _RasterizeGaussiansAuxAbs, (True, True, True): _RasterizeGaussiansAuxDepthAbs}
 
 
 def _empty_if_none(t):

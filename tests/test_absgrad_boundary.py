@@ -100,6 +100,43 @@ def test_python_surface_is_opt_in():
     assert len(dgr.GaussianRasterizationSettings._fields) == 12  # the settings tuple does not change
 
 
+def test_flags_select_one_of_eight_distinct_functions(monkeypatch):
+    """rasterize_gaussians hands its nine arguments to the Function of its (depth_grad, alpha, absgrad) triple; no
+    Function runs here (every .apply is a recorder)"""
+    import diff_gaussian_rasterization as dgr
+    table = {(False, False, False): "_RasterizeGaussians",
+             (True, False, False): "_RasterizeGaussiansDepth",
+             (False, True, False): "_RasterizeGaussiansAux",
+             (True, True, False): "_RasterizeGaussiansAuxDepth",
+             (False, False, True): "_RasterizeGaussiansAbs",
+             (True, False, True): "_RasterizeGaussiansAbsDepth",
+             (False, True, True): "_RasterizeGaussiansAuxAbs",
+             (True, True, True): "_RasterizeGaussiansAuxDepthAbs"}
+    classes = [getattr(dgr, n) for n in table.values()]
+    assert len(set(classes)) == 8
+    for c in classes:
+        assert issubclass(c, torch.autograd.Function)
+    assert len(dgr.__all__) == 11 and set(table.values()) < set(dgr.__all__)
+    for n in dgr.__all__:
+        assert getattr(dgr, n) is not None, n
+    calls = []
+    for n, c in zip(table.values(), classes):
+        monkeypatch.setattr(c, "apply", staticmethod(lambda *a, n=n: calls.append((n, a)) or n))
+    args = tuple(object() for _ in range(9))
+    for (depth_grad, alpha, absgrad), want in table.items():
+        assert dgr.rasterize_gaussians(*args, depth_grad=depth_grad, alpha=alpha, absgrad=absgrad) == want
+        assert calls[-1][0] == want and all(x is y for x, y in zip(calls[-1][1], args)) and len(calls[-1][1]) == 9
+    assert dgr.rasterize_gaussians(*args) == "_RasterizeGaussians"  # every flag defaults to off
+    assert len(calls) == 9
+    # the module passes its three flags on
+    e = torch.zeros(4, 4)
+    st = dgr.GaussianRasterizationSettings(8, 8, 0.5, 0.5, torch.ones(3), 1.0, e, e, 0, torch.zeros(3), False, False)
+    z = torch.zeros(4, 3)
+    for triple, want in table.items():
+        r = dgr.GaussianRasterizer(st, depth_grad=triple[0], alpha=triple[1], absgrad=triple[2])
+        assert r(means3D=z, means2D=z, opacities=z[:, :1], shs=z, scales=z, rotations=z) == want
+
+
 def test_reference_signed_sum_is_the_restatements_gradient(oracle):
     """the per-(pixel, slot) leaf's gradient, scatter-added with its sign, is the existing restatement's ndc_off
     gradient to 1e-12 (asserted inside the helper); its absolute scatter-sum dominates it and is not the same"""

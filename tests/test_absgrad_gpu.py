@@ -204,6 +204,62 @@ def test_autograd_surface_composes_and_overwrites(oracle):
     assert torch.equal(L["means2D"].absgrad, 2 * first)  # a power of two scales every term exactly
 
 
+def test_autograd_matrix_is_the_direct_entries_tuple():
+    """Every (depth_grad, alpha, absgrad) Function, with the loss built from the colour image only, the depth image
+    only, the alpha image only (where there is one) and all of them: each leaf's .grad is, bit for bit, the tensor
+    of the direct _C entry the Function stands for, called on the same scene's forward buffers with zeros / empty
+    tensors for what the loss did not use; where nothing can flow (only the depth image used without depth_grad)
+    every leaf stays without .grad and means2D without .absgrad.  small0: P = 60, 70 x 45 (partial tiles)."""
+    name = "small0"
+    sc, g = DS.scene(name), TD.gpu_forward(name)
+    s, d = sc["s"], g["d"]
+    gen = torch.Generator().manual_seed(11)
+    g_c, g_d, g_a = (torch.randn(c, s["H"], s["W"], generator=gen).to("cuda:0") for c in (3, 1, 1))
+    e = torch.empty(0, device="cuda:0")
+    # position of each leaf's gradient in the entries' tuple
+    slot = {"means3D": 3, "means2D": 0, "shs": 5, "opacities": 2, "scales": 6, "rotations": 7}
+
+    def direct(entry, *grads):
+        return _call(entry, s, d, g["fwd"], list(grads), colors=g["colors"], cov3D=g["cov3D"], use_sh=sc["use_sh"])
+
+    for absgrad in (False, True):
+        for alpha in (False, True):
+            for depth_grad in (False, True):
+                every = ("c", "d", "a") if alpha else ("c", "d")
+                for use in [("c",), ("d",)] + ([("a",)] if alpha else []) + [every]:
+                    what = (depth_grad, alpha, absgrad, use)
+                    L, out = _raster(s, d, depth_grad=depth_grad, alpha=alpha, absgrad=absgrad)
+                    assert len(out) == (4 if alpha else 3)
+                    up = {"c": (0, g_c), "d": (2, g_d), "a": (3, g_a)}
+                    sum((out[up[k][0]] * up[k][1]).sum() for k in use).backward()
+                    gc = g_c if "c" in use else None
+                    gd = g_d if "d" in use and depth_grad else None  # dropped unless depth_grad is set
+                    ga = g_a if "a" in use else None
+                    if gc is None and gd is None and ga is None:
+                        assert all(t.grad is None for t in L.values()), what
+                        assert not hasattr(L["means2D"], "absgrad"), what
+                        continue
+                    if alpha or absgrad:  # a missing colour gradient is zeros, a missing depth / alpha one is empty
+                        want = direct("rasterize_gaussians_backward_absgrad" if absgrad
+                                      else "rasterize_gaussians_backward_aux",
+                                      torch.zeros_like(g_c) if gc is None else gc, e if gd is None else gd,
+                                      e if ga is None else ga)
+                    elif depth_grad:  # both as zeros
+                        want = direct("rasterize_gaussians_backward_depth",
+                                      torch.zeros_like(g_c) if gc is None else gc,
+                                      torch.zeros_like(g_d) if gd is None else gd)
+                    else:
+                        want = direct("rasterize_gaussians_backward", gc)
+                    assert len(want) == (9 if absgrad else 8)
+                    for k, t in L.items():
+                        assert t.grad is not None and torch.equal(t.grad, want[slot[k]]), (k, what)
+                    assert want[0].abs().max() > 0
+                    if absgrad:
+                        assert torch.equal(L["means2D"].absgrad, want[8]) and want[8].abs().max() > 0, what
+                    else:
+                        assert not hasattr(L["means2D"], "absgrad"), what
+
+
 # ---- edges ----
 def test_empty_culled_and_partly_culled_scenes():
     dev = torch.device("cuda:0")

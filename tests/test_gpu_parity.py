@@ -124,6 +124,21 @@ def test_parity_scale_modifier_and_big_splats(C, oracle, dev):
     _check(C, oracle, s, dev)
 
 
+def test_parity_frustum_clamp_and_independent_fovy(C, oracle, dev):
+    """Splats centred beyond the 1.3 tan_fov frustum clamp of computeCov2D (forward.cu:83-87, backward.cu:165-170,
+    262-264) that still overlap the image, seen by a rotated camera whose fovy is independent of fovx and the aspect
+    ratio (focal_x != focal_y): the small scenes of tests/rule_scenes.py at scale, against the oracle."""
+    import rule_scenes as RS
+    s = RS.view_with_camera(make_scene(3000, 160, 96, seed=32, spread=1.7, log_scale=math.log(0.1)), rescale_y=False)
+    fx, fy = s["W"] / (2 * s["tanfovx"]), s["H"] / (2 * s["tanfovy"])
+    assert abs(fx - fy) > 0.05 * fx
+    fwd, _ = _check(C, oracle, s, dev)
+    view = s["viewmatrix"].astype(np.float64).reshape(4, 4)
+    t = (np.c_[s["means3D"].astype(np.float64), np.ones(3000)] @ view)[:, :3]
+    clamped = (np.abs(t[:, 0] / t[:, 2]) > 1.3 * s["tanfovx"]) | (np.abs(t[:, 1] / t[:, 2]) > 1.3 * s["tanfovy"])
+    assert int((clamped & (fwd[3].cpu().numpy() > 0)).sum()) >= 100
+
+
 def test_parity_opaque_stack_termination(C, oracle, dev):
     """Many nearly opaque splats: exercises the 0.99 clamp and the T < 1e-4 early exit."""
     s = make_scene(6000, 128, 128, seed=13, log_scale=math.log(0.1))

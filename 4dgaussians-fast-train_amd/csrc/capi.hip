@@ -221,6 +221,17 @@ int gs4d_debug_pair_alpha(int P, int width, int height, const char *geometry_buf
     GS4D_HIP(launch_pair_alpha(g, n, gid, px, py, og, pw, (hipStream_t)stream_));
     return GS4D_OK;
 }
+int gs4d_debug_wave_sum(int n, const float *in, int depth, int abs, float *out_lds, float *out_permlane,
+                        void *stream_) {
+    if (n < 0 || (n > 0 && (!in || !out_lds || !out_permlane))) return fail(GS4D_ERR_ARG, "debug_wave_sum: bad args");
+    GS4D_HIP(launch_wave_sum_debug(n, in, depth != 0, abs != 0, out_lds, out_permlane, (hipStream_t)stream_));
+    return GS4D_OK;
+}
+int gs4d_debug_backward_occupancy(int depth, int abs, int *workgroups_per_cu) {
+    if (!workgroups_per_cu) return fail(GS4D_ERR_ARG, "debug_backward_occupancy: bad args");
+    GS4D_HIP(render_backward_occupancy(depth != 0, abs != 0, workgroups_per_cu));
+    return GS4D_OK;
+}
 int gs4d_mark_visible_ex(int P, const float *means3D, const float *viewmatrix, const float *projmatrix,
                          uint8_t *present, void *stream_, int view_transposed) {
     hipStream_t stream = (hipStream_t)stream_;

@@ -211,6 +211,11 @@ hipError_t launch_pair_alpha(GeomState g, int n, const int *gid, const int *px, 
 hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gid_by_e, const uint32_t *upos,
                                   ImageState img, const float *dL_dpix, const float *dL_ddepth,
                                   const float *dL_dalpha, bool abs, float *contrib, hipStream_t s);
+// gs4d_debug_wave_sum / gs4d_debug_backward_occupancy: the blend's pair reduction on given inputs, through LDS
+// column sums and through permlane swaps, and the resident workgroups per CU of a blend instantiation
+hipError_t launch_wave_sum_debug(int n, const float *in, bool depth, bool abs, float *out_lds, float *out_permlane,
+                                 hipStream_t s);
+hipError_t render_backward_occupancy(bool depth, bool abs, int *workgroups_per_cu);
 size_t contrib_scratch_bytes(int R, int P);
 hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,

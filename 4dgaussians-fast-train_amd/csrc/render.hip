@@ -19,7 +19,7 @@
 // (A = alpha CD + (1 - alpha) A, the same recurrence as backward.cu:515-517).  The 9 gradient terms of
 // a splat (backward.cu:523,545-554) are linear in 6 per-pixel moments (sum u, sum u dx, sum u dy,
 // sum u dx^2, sum u dx dy, sum u dy^2 with u = G dL/dalpha) and 3 colour sums; these 9 values are
-// reduced over the wave with two v_permlane swaps and a 16-lane DPP tree (reduce-scatter), staged in
+// reduced over the wave with column sums through LDS and a 16-lane DPP tree (reduce-scatter), staged in
 // LDS, and stored once per (tile, splat) instance at its emission slot (coalesced 48-byte records,
 // no float atomics).  The per-Gaussian pass (preprocess_backward.hip) sums a Gaussian's records in
 // a fixed order and applies the moment -> gradient map once (bitwise reproducible).
@@ -354,7 +354,8 @@ __global__ __launch_bounds__(128) void render_forward_kernel(Args a, const uint2
         read_raw_lds(nxt, s_raw, lane, valid, yc, false);  // this wave's own staging: no block barrier
         nxt.reach = valid ? rnxt : 0u;
         const uint64_t reach = ballot((nxt.reach >> h) & 1u);
-        const uint64_t nonpd = ballot(!conic_pd(nxt.geo, nxt.opc));
+        // per-splat wave masks (the staged zero splats past a partial batch are neither)
+        const uint64_t nonpd = ballot(valid && !conic_pd(nxt.geo, nxt.opc));
         const bool cap = ballot(valid && nxt.opc.z < kInvCapFree) != 0;  // wave-uniform: a splat the 0.99 cap can bind
         // one wave writes and reads its own staging area: LDS operations of a wave complete in order
         __builtin_amdgcn_wave_barrier();
@@ -489,11 +490,37 @@ struct SplatPart {
     float u0, u1, u2, w0, w1, w2;
 };
 
+// Column sums of one register quadruple through the wave's 1 KiB transpose buffer `col` (one round): every lane
+// stores its four values, lane (g = lane / 16, c = lane % 16) reads value g of the four lanes (r, c) of its column
+// and adds them as (row 0 + row 2) + (row 1 + row 3) -- the association v_permlane32_swap then v_permlane16_swap
+// and their adds give, so the result is theirs to the bit.  LDS instructions take no VALU issue cycles: a round
+// costs the VALU its 3 adds, against 3 swaps (8.25 issue cycles each, tools/bench/valu_rates.hip) and 3 adds.
+// Layout: (v0, v1) as one float2 at word 2 lane, (v2, v3) at word 128 + 2 lane, so value g of lane (r, c) lies
+// at word 128 (g / 2) + 32 r + 2 c + g % 2.  A 4-byte read banks on (word mod 32) within each 32-lane group
+// (MI355X: ds_read_b32): the group's lanes have g / 2 and r in common and 2 c + g % 2 covers 0..31 once -- no
+// conflict (one float4 per lane at word 4 lane would put columns c and c + 8 on one bank); the 8-byte stores
+// are lane-contiguous.  One wave is the workgroup and a wave's LDS operations complete in order, so rounds
+// reuse the buffer with no s_barrier and no wait: the wave barriers only keep the compiler from reordering
+// the stores and loads, and each read is waited for (counted lgkmcnt) where its add consumes it.
+constexpr int kColSumWords = 256;
+__device__ __forceinline__ float lds_col_sum(float *col, int lane, float v0, float v1, float v2, float v3) {
+    float2 *st = reinterpret_cast<float2 *>(col) + lane;
+    st[0] = make_float2(v0, v1);
+    st[64] = make_float2(v2, v3);
+    __builtin_amdgcn_wave_barrier();
+    const float *rd = col + ((lane >> 5) << 7) + ((lane & 15) << 1) + ((lane >> 4) & 1);
+    const float p0 = rd[0], p1 = rd[32], p2 = rd[64], p3 = rd[96];
+    __builtin_amdgcn_wave_barrier();
+    return (p0 + p2) + (p1 + p3);
+}
+
 // Wave64 totals of two splats' partial sums, left in LDS as their 9 record values:
 //   0 sum u, 1 sum dx u, 2 sum u yl, 3 sum dx^2 u, 4 sum dx u yl, 5 sum u yl^2, 6-8 colour sums
-// (dx = mean.x - pixel x, per lane column).  v_permlane32_swap then v_permlane16_swap sum each value
-// over the 4 lanes of a column (reduce-scatter: row r of x1 ends with (a.u0, a.u1, b.u0, b.u1)[r], of x2
-// (a.u2, a.w0, b.u2, b.w0)[r], of x3 (a.w1, a.w2, b.w1, b.w2)[r]); the dx-weighted moments x4, x5 are
+// (dx = mean.x - pixel x, per lane column).  Each value is first summed over the 4 lanes of a column
+// (reduce-scatter: row r of x1 ends with (a.u0, a.u1, b.u0, b.u1)[r], of x2 (a.u2, a.w0, b.u2, b.w0)[r], of
+// x3 (a.w1, a.w2, b.w1, b.w2)[r]) by three rounds of lds_col_sum() (COLS_LDS, the blend's form; the DEPTH value
+// and the ABS pair take a round each), or by v_permlane32_swap then v_permlane16_swap (the earlier form, kept
+// as the reference of gs4d_debug_wave_sum only: same bits); the dx-weighted moments x4, x5 are
 // formed on those column sums.  The 16 columns of each row are then reduce-scattered too, with DPP:
 // pairs of registers halve at each of the four stages (column c with c ^ 8, the half-row mirror, c ^ 2,
 // c ^ 1), so every lane ends with one finished total (15 DPP-stage instructions for the 5 registers
@@ -521,19 +548,31 @@ __device__ __forceinline__ int red_offset(int lane) {
     default: return -1;
     }
 }
-template <bool DEPTH, bool ABS>
+template <bool DEPTH, bool ABS, bool COLS_LDS = true>
 __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const SplatPart &b, float dxa, float dxb,
                                                      float w3a, float w3b, float axa, float aya, float axb, float ayb,
-                                                     float *rec_pair, int lane, int roff) {
-    const float h0 = swap32_add(a.u0, b.u0);  // lanes 0-31: a, 32-63: b
-    const float h1 = swap32_add(a.u1, b.u1);
-    const float h2 = swap32_add(a.u2, b.u2);
-    const float h3 = swap32_add(a.w0, b.w0);
-    const float h4 = swap32_add(a.w1, b.w1);
-    const float h5 = swap32_add(a.w2, b.w2);
-    const float x1 = swap16_add(h0, h1);
-    const float x2 = swap16_add(h2, h3);
-    const float x3 = swap16_add(h4, h5);
+                                                     float *col, float *rec_pair, int lane, int roff) {
+    // x6 (DEPTH): rows 1 and 3 hold the column sums of a's and b's W3; x7 (ABS) = (a.AX, a.AY, b.AX, b.AY)
+    float x1, x2, x3, x6 = 0.f, x7 = 0.f;
+    if (COLS_LDS) {
+        x1 = lds_col_sum(col, lane, a.u0, a.u1, b.u0, b.u1);
+        x2 = lds_col_sum(col, lane, a.u2, a.w0, b.u2, b.w0);
+        x3 = lds_col_sum(col, lane, a.w1, a.w2, b.w1, b.w2);
+        if (DEPTH) x6 = lds_col_sum(col, lane, 0.f, w3a, 0.f, w3b);
+        if (ABS) x7 = lds_col_sum(col, lane, axa, aya, axb, ayb);
+    } else {
+        const float h0 = swap32_add(a.u0, b.u0);  // lanes 0-31: a, 32-63: b
+        const float h1 = swap32_add(a.u1, b.u1);
+        const float h2 = swap32_add(a.u2, b.u2);
+        const float h3 = swap32_add(a.w0, b.w0);
+        const float h4 = swap32_add(a.w1, b.w1);
+        const float h5 = swap32_add(a.w2, b.w2);
+        x1 = swap16_add(h0, h1);
+        x2 = swap16_add(h2, h3);
+        x3 = swap16_add(h4, h5);
+        if (DEPTH) x6 = swap16_add(0.f, swap32_add(w3a, w3b));
+        if (ABS) x7 = swap16_add(swap32_add(axa, axb), swap32_add(aya, ayb));
+    }
     const float dxs = lane < 32 ? dxa : dxb;  // rows 0-1 hold splat a, rows 2-3 splat b
     const float x4 = x1 * dxs;                 // (dx a.u0, dx a.u1, dx b.u0, dx b.u1)
     const float x5 = x4 * dxs;                 // (dx^2 a.u0, -, dx^2 b.u0, -)
@@ -543,10 +582,9 @@ __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const S
     const float z34 = (c8 ? x3 : x4) + dpp<0x128>(c8 ? x4 : x3);
     float z5 = x5 + dpp<0x128>(x5);
     if (DEPTH) {
-        // one more swap pair: rows 1 and 3 of x6 hold the column sums of a's and b's W3, which take z5's unused
-        // odd rows from here on (one DPP move more).  They join after x5's own stage A so that the even rows'
-        // arithmetic is the colour-only kernel's to the bit (x5's product and add contract into one fma there).
-        const float x6 = swap16_add(0.f, swap32_add(w3a, w3b));
+        // x6's odd rows take z5's unused odd rows from here on (one DPP move more).  They join after x5's own
+        // stage A so that the even rows' arithmetic is the colour-only kernel's to the bit (x5's product and add
+        // contract into one fma there).
         const float z6 = x6 + dpp<0x128>(x6);
         z5 = (lane & 16) ? z6 : z5;
     }
@@ -556,7 +594,6 @@ __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const S
     if (ABS) {
         // x7 takes its own stage A (sums only, no product) and the half of z5's stage B that carried copies: the
         // columns with bit 2 clear keep x5's sums in x5's order (the bits of S dx^2 u and W3 stay), the others x7's
-        const float x7 = swap16_add(swap32_add(axa, axb), swap32_add(aya, ayb));
         const float z7 = x7 + dpp<0x128>(x7);
         w5 = (c4 ? z5 : z7) + dpp<0x141>(c4 ? z7 : z5);
     } else {
@@ -566,6 +603,39 @@ __device__ __forceinline__ void wave_sum_pair_to_lds(const SplatPart &a, const S
     const float v = (c2 ? w : w5) + dpp<0x4E>(c2 ? w5 : w);  // quad_perm [2, 3, 0, 1]
     const float u = v + dpp<0xB1>(v);                         // quad_perm [1, 0, 3, 2]
     if (roff >= 0) rec_pair[roff] = u;
+}
+
+// Diagnostic (gs4d_debug_wave_sum): one wave per pair of splats runs wave_sum_pair_to_lds on given per-lane
+// inputs, `in` = n x kWaveSumInputs x 64 floats (value k of lane l of pair p at (p kWaveSumInputs + k) 64 + l):
+// k = 0-5 a's (u0, u1, u2, w0, w1, w2), 6-11 b's, 12-13 W3 of a and b, 14-17 (a.AX, a.AY, b.AX, b.AY), 18-19 the
+// lanes' dx of a and b.  out = n x 24: the two records as the blend's s_rec holds them (floats no lane writes: 0).
+constexpr int kWaveSumInputs = 20;
+template <bool DEPTH, bool ABS, bool COLS_LDS>
+__global__ __launch_bounds__(64) void wave_sum_debug_kernel(const float *__restrict__ in, float *__restrict__ out) {
+    __shared__ float s_col[kColSumWords];
+    __shared__ float s_rec[24];
+    const int lane = threadIdx.x;
+    const float *p = in + ((size_t)blockIdx.x * kWaveSumInputs) * 64 + lane;
+    if (lane < 24) s_rec[lane] = 0.f;
+    __syncthreads();
+    const SplatPart a{p[0], p[64], p[128], p[192], p[256], p[320]};
+    const SplatPart b{p[384], p[448], p[512], p[576], p[640], p[704]};
+    wave_sum_pair_to_lds<DEPTH, ABS, COLS_LDS>(a, b, p[18 * 64], p[19 * 64], p[12 * 64], p[13 * 64], p[14 * 64],
+                                               p[15 * 64], p[16 * 64], p[17 * 64], s_col, s_rec, lane,
+                                               red_offset<DEPTH, ABS>(lane));
+    __syncthreads();
+    if (lane < 24) out[(size_t)blockIdx.x * 24 + lane] = s_rec[lane];
+}
+hipError_t launch_wave_sum_debug(int n, const float *in, bool depth, bool abs, float *out_lds, float *out_permlane,
+                                 hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    return with_backward_variant(depth, abs, [&](auto depth_c, auto abs_c) {
+        hipLaunchKernelGGL((wave_sum_debug_kernel<depth_c.value, abs_c.value, true>), dim3(n), dim3(64), 0, s, in,
+                           out_lds);
+        hipLaunchKernelGGL((wave_sum_debug_kernel<depth_c.value, abs_c.value, false>), dim3(n), dim3(64), 0, s, in,
+                           out_permlane);
+        return hipGetLastError();
+    });
 }
 
 // Per-pixel state of the reverse walk (pairs): T (recovered backwards), A = accum_rec . dL/dpix and
@@ -715,6 +785,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_waves(DE
     constexpr int NU = 6 + (DEPTH ? 1 : 0) + (ABS ? 2 : 0);
     __shared__ SplatLDS s_sp[64];
     __shared__ float4 s_rec[64][3];  // reduced sums of the batch's splats
+    // the reduction's transpose buffer: 10,240 B of LDS per workgroup with it, 16 workgroups on a CU's 160 KiB
+    __shared__ float s_col[kColSumWords];
     const int tile = (int)__builtin_amdgcn_readfirstlane(order[blockIdx.x]);  // longest runs first
     const int tx = tile % a.gx, ty = tile / a.gx;
     const int lane = threadIdx.x;
@@ -886,8 +958,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bwd_waves(DE
             wave_sum_pair_to_lds<DEPTH, ABS>(part[0], part[1], dxs[0], dxs[1], DEPTH ? hsum(U[0][6]) : 0.f,
                                              DEPTH ? hsum(U[1][6]) : 0.f, ABS ? hsum(U[0][NU - 2]) : 0.f,
                                              ABS ? hsum(U[0][NU - 1]) : 0.f, ABS ? hsum(U[1][NU - 2]) : 0.f,
-                                             ABS ? hsum(U[1][NU - 1]) : 0.f, reinterpret_cast<float *>(s_rec[j]),
-                                             lane, roff);
+                                             ABS ? hsum(U[1][NU - 1]) : 0.f, s_col,
+                                             reinterpret_cast<float *>(s_rec[j]), lane, roff);
         };
         using I3 = std::integral_constant<int, 3>;
         auto walk_batch = [&](auto all) {
@@ -957,6 +1029,15 @@ hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gi
                            img.order, gid_by_e, upos, g.splat, img.final_T, img.n_contrib, dL_dpix, dL_ddepth, dL_dalpha,
                            contrib);
         return hipGetLastError();
+    });
+}
+
+// how many of an instantiation's single-wave workgroups the runtime keeps resident on one CU (registers and LDS):
+// 4 waves per SIMD are 16, the absgrad instantiations' 3 are 12
+hipError_t render_backward_occupancy(bool depth, bool abs, int *workgroups_per_cu) {
+    return with_backward_variant(depth, abs, [&](auto depth_c, auto abs_c) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            workgroups_per_cu, render_backward_kernel<depth_c.value, abs_c.value>, 64, 0);
     });
 }
 

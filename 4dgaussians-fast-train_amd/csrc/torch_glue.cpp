@@ -347,9 +347,32 @@ std::tuple<torch::Tensor, torch::Tensor> DebugPairAlpha(const torch::Tensor &geo
     return {og, pw};
 }
 
+// reduction diagnostic: inputs n x 20 x 64 fp32 -> the n x 24 records by LDS column sums and by permlane swaps
+std::tuple<torch::Tensor, torch::Tensor> DebugWaveSum(const torch::Tensor &in_, bool depth, bool abs) {
+    TORCH_CHECK(in_.is_cuda() && in_.dim() == 3 && in_.size(1) == 20 && in_.size(2) == 64,
+                "debug_wave_sum: a device tensor n x 20 x 64");
+    const c10::hip::HIPGuard guard(in_.device().index());
+    auto in = in_.to(torch::kFloat32).contiguous();
+    const int n = (int)in.size(0);
+    auto out_lds = torch::empty({n, 24}, in.options());
+    auto out_permlane = torch::empty({n, 24}, in.options());
+    const int st = gs4d_debug_wave_sum(n, in.data_ptr<float>(), depth, abs, out_lds.data_ptr<float>(),
+                                       out_permlane.data_ptr<float>(),
+                                       c10::hip::getCurrentHIPStream(in.device().index()).stream());
+    TORCH_CHECK(st == 0, "debug_wave_sum: ", gs4d_last_error());
+    return {out_lds, out_permlane};
+}
+static int DebugBackwardOccupancy(bool depth, bool abs) {
+    int wgs = 0;
+    TORCH_CHECK(gs4d_debug_backward_occupancy(depth, abs, &wgs) == 0, "debug_backward_occupancy: ", gs4d_last_error());
+    return wgs;
+}
+
 PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians", &RasterizeGaussians);
     m.def("debug_pair_alpha", &DebugPairAlpha);
+    m.def("debug_wave_sum", &DebugWaveSum);
+    m.def("debug_backward_occupancy", &DebugBackwardOccupancy);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
     m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);
     m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux);

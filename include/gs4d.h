@@ -222,6 +222,21 @@ int gs4d_voxel_downsample(int N, const float *points, const float *colors, doubl
 int gs4d_debug_pair_alpha(int P, int width, int height, const char *geometry_buffer, int n, const int *gid,
                           const int *px, const int *py, float *og, float *pw, void *stream);
 
+/* Diagnostic for the blend backward's pair reduction (no reference counterpart): n pairs of splats, one wave
+ * each, reduce given per-lane partial sums to their two 12-float records, once as the blend kernel does (column
+ * sums through LDS) and once by permlane swaps (the earlier form, kept for this comparison): the two must agree
+ * to the bit.  in: n x 20 x 64 fp32 on the device, value k of lane l of pair p at (20 p + k) 64 + l, with
+ * k = 0-5 splat a's (u0, u1, u2, w0, w1, w2), 6-11 splat b's, 12-13 W3 of a and b, 14-17 (a.AX, a.AY, b.AX, b.AY),
+ * 18-19 the lanes' dx of a and b.  depth / abs select the instantiation (W3 and the absolute sums are read only
+ * by theirs).  out_lds / out_permlane: n x 24 fp32, a's record then b's; floats the instantiation does not
+ * produce are 0. */
+int gs4d_debug_wave_sum(int n, const float *in, int depth, int abs, float *out_lds, float *out_permlane,
+                        void *stream);
+
+/* How many workgroups (one wave each) of the blend backward's (depth, abs) instantiation the runtime keeps
+ * resident on one CU, by its registers and LDS: 4 waves per SIMD are 16, 3 are 12. */
+int gs4d_debug_backward_occupancy(int depth, int abs, int *workgroups_per_cu);
+
 /* Human-readable message for the last error on this thread (never NULL). */
 const char *gs4d_last_error(void);
 

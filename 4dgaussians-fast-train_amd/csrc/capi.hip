@@ -245,13 +245,23 @@ int gs4d_mark_visible(int P, const float *means3D, const float *viewmatrix, cons
     return gs4d_mark_visible_ex(P, means3D, viewmatrix, projmatrix, present, stream, 0);
 }
 
-int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
+int gs4d_debug_effective_opacity(int P, const char *geometry_buffer, float *out, void *stream_) {
+    if (P < 0 || (P > 0 && (!geometry_buffer || !out))) return fail(GS4D_ERR_ARG, "debug_effective_opacity: bad args");
+    if (P == 0) return GS4D_OK;
+    // conic_opacity is carved ahead of the arrays whose size depends on the tile count
+    GeomState g = GeomState::carve(const_cast<char *>(geometry_buffer), P, 1);
+    GS4D_HIP(launch_effective_opacity(P, g, out, (hipStream_t)stream_));
+    return GS4D_OK;
+}
+
+int gs4d_forward_aa(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
                     gs4d_alloc_fn image_alloc, void *image_ctx, int P, int D, int M, const float *background,
                     int width, int height, const float *means3D, const float *shs, const float *colors_precomp,
                     const float *opacities, const float *scales, float scale_modifier, const float *rotations,
                     const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix,
                     const float *cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
-                    float *out_depth, int *radii, int debug, void *stream_, int *num_rendered, int view_transposed) {
+                    float *out_depth, int *radii, int debug, void *stream_, int *num_rendered, int view_transposed,
+                    int antialiasing) {
     hipStream_t stream = (hipStream_t)stream_;
     *num_rendered = 0;
     if (P < 0 || width <= 0 || height <= 0) return fail(GS4D_ERR_ARG, "forward: P must be >= 0 and the image non-empty");
@@ -286,7 +296,8 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
     // one memset: prefiltered flag, num_rendered shards, depth-sort histograms and look-back words
     GS4D_HIP(hipMemsetAsync(g.zero, 0, 4 * geom_zero_words(P), stream));
     GS4D_STAGE("preprocess", launch_preprocess(a, means3D, scales, rotations, opacities, shs, cov3D_precomp,
-                                               colors_precomp, radii_ptr, g, (int *)(g.zero + kZeroFlag), stream));
+                                               colors_precomp, radii_ptr, g, (int *)(g.zero + kZeroFlag),
+                                               antialiasing != 0, stream));
 
     // H1: the single device->host synchronisation of the forward (rasterizer_impl.cu:282).  The scan of
     // the visible Gaussians is enqueued before the host waits, so the GPU keeps working during the
@@ -330,9 +341,22 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
     return GS4D_OK;
 }
 
+int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
+                    gs4d_alloc_fn image_alloc, void *image_ctx, int P, int D, int M, const float *background,
+                    int width, int height, const float *means3D, const float *shs, const float *colors_precomp,
+                    const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                    const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix,
+                    const float *cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
+                    float *out_depth, int *radii, int debug, void *stream, int *num_rendered, int view_transposed) {
+    return gs4d_forward_aa(geometry_alloc, geometry_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M,
+                           background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
+                           rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
+                           out_color, out_depth, radii, debug, stream, num_rendered, view_transposed, 0);
+}
+
 }  // extern "C"
 
-// One backward call, as the six exported entries hand it to backward_impl: gs4d_backward_absgrad's parameters in
+// One backward call, as the seven exported entries hand it to backward_impl: gs4d_backward_absgrad's parameters in
 // their order, then what the entry requires.
 namespace {
 struct BackwardCall {
@@ -354,6 +378,7 @@ struct BackwardCall {
     void *stream;
     int view_transposed;
     bool need_depth, need_abs;  // gs4d_backward_depth / gs4d_backward_absgrad: a NULL dL_ddepth / abs_dmean2D is an error
+    const float *aa_opacities = nullptr;  // gs4d_backward_aa with antialiasing: the forward's raw opacities
 };
 }  // namespace
 
@@ -411,7 +436,7 @@ static int backward_impl(const BackwardCall &c) {
                launch_gaussian_backward(a, g, R, reduce_scratch, depth, radii_ptr, c.means3D, c.shs, c.scales,
                                         c.rotations, cov3D_ptr, c.dL_dmean2D, dconic, c.dL_dopacity, c.dL_dcolor,
                                         c.dL_dmean3D, c.dL_dcov3D, c.dL_dsh, c.dL_dscale, c.dL_drot, c.abs_dmean2D,
-                                        stream));
+                                        c.aa_opacities, stream));
     if (c.dL_dconic && (float *)dconic != c.dL_dconic)
         GS4D_HIP(hipMemcpyAsync(c.dL_dconic, dconic, 16 * (size_t)P, hipMemcpyDeviceToDevice, stream));
     end_marks();
@@ -483,6 +508,25 @@ int gs4d_backward_absgrad(int P, int D, int M, int R, const float *background, i
                           geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dalpha, dL_dmean2D,
                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
                           abs_dmean2D, scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, true});
+}
+
+int gs4d_backward_aa(int P, int D, int M, int R, const float *background, int width, int height,
+                     const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                     float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                     const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                     float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                     const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
+                     float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                     float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D, gs4d_alloc_fn scratch_alloc,
+                     void *scratch_ctx, int debug, void *stream, int view_transposed, const float *opacities,
+                     int antialiasing) {
+    if (antialiasing && !opacities && P != 0) return fail(GS4D_ERR_ARG, "backward_aa: antialiasing needs the forward's opacities");
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dalpha, dL_dmean2D,
+                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                          abs_dmean2D, scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, false,
+                          antialiasing ? opacities : nullptr});
 }
 
 int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out_alpha, void *stream) {

@@ -192,7 +192,10 @@ __device__ __forceinline__ uint32_t xor_lane(uint32_t v, int lx) {
 // ---- launchers (each enqueues on `stream`, returns hipError_t of the launch) ------------------
 hipError_t launch_preprocess(const Args &a, const float *means3D, const float *scales, const float *rotations,
                              const float *opacities, const float *shs, const float *cov3D_precomp,
-                             const float *colors_precomp, int *radii, GeomState g, int *err_flag, hipStream_t s);
+                             const float *colors_precomp, int *radii, GeomState g, int *err_flag, bool antialiasing,
+                             hipStream_t s);
+// gs4d_debug_effective_opacity: out[i] = conic_opacity[i].w (o, or o * s after an antialiased forward)
+hipError_t launch_effective_opacity(int P, GeomState g, float *out, hipStream_t s);
 hipError_t launch_mark_visible(int P, const float *means3D, const float *viewmatrix, int view_transposed,
                                uint8_t *present, hipStream_t s);
 hipError_t launch_visible_scan(const Args &a, GeomState g, hipStream_t s);
@@ -221,13 +224,14 @@ hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int
                                  char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
                                  float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s);
 // also finishes the contrib_reduce sums of Gaussians spanning waves (same scratch) and zero-fills the
-// render-level gradients of Gaussians without instances
+// render-level gradients of Gaussians without instances.  opacities (NULL for none): the raw opacities of an
+// antialiased forward, which select the instantiations that chain dL_dopacity through s = o_eff / o
 hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scratch, bool depth, const int *radii,
                                     const float *means3D, const float *shs, const float *scales,
                                     const float *rotations, const float *cov3D, float *dL_dmean2D,
                                     float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                                     float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                    float *abs_dmean2D, hipStream_t s);
+                                    float *abs_dmean2D, const float *opacities, hipStream_t s);
 // The two run-time flags as compile-time constants: f(std::bool_constant<depth>{}, std::bool_constant<abs>{}),
 // for the launchers' choice among a kernel's four instantiations.
 template <class F>

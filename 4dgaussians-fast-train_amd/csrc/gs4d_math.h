@@ -129,9 +129,33 @@ __device__ __forceinline__ void computeCov3D(V3 scale, float mod, float4 rot, fl
     cov[3] = Sigma.m[1][1]; cov[4] = Sigma.m[1][2]; cov[5] = Sigma.m[2][2];
 }
 
-// forward.cu:74-113 -> (a, b, c) of the 2x2 screen-space covariance incl. the +0.3 low-pass
+// Antialiased rasterization (opt-in; Mip-Splatting's 2-D filter, no reference counterpart): the +0.3 low-pass
+// widens the footprint of a splat and leaves its opacity, so a sub-pixel splat deposits more energy than it
+// holds.  The compensation scales the opacity by s = sqrt(max(kAAFloor, r)), r = D0 / D1, the determinants of
+// the projected covariance before (a0, b, c0) and after (a0 + 0.3, b, c0 + 0.3) the low-pass.  The forward
+// (preprocess.hip) and the backward (cov2D_backward) both take D0, D1, r and the floor test from here, in
+// files compiled without contraction, so the two take the same side of the floor for the same Gaussian.
+// A floored s is a constant of the backward (dL/dr = 0); a NaN r counts as floored.
+constexpr float kAAFloor = 2.5e-5f;
+struct AAFactor {
+    float D0, D1, r, s;
+    bool floored;
+};
+__device__ __forceinline__ AAFactor aa_factor(float a0, float b, float c0) {
+    AAFactor f;
+    const float a = a0 + 0.3f, c = c0 + 0.3f;
+    f.D0 = a0 * c0 - b * b;
+    f.D1 = a * c - b * b;
+    f.r = f.D0 / f.D1;
+    f.floored = !(f.r > kAAFloor);
+    f.s = sqrtf(f.floored ? kAAFloor : f.r);
+    return f;
+}
+
+// forward.cu:74-113 -> (a, b, c) of the 2x2 screen-space covariance incl. the +0.3 low-pass; raw (when given)
+// receives (a0, b, c0), the entries before it
 __device__ __forceinline__ float3 computeCov2D(V3 mean, float focal_x, float focal_y, float tan_fovx, float tan_fovy,
-                                               const float cov3D[6], const Mat4 &view) {
+                                               const float cov3D[6], const Mat4 &view, float3 *raw = nullptr) {
     V3 t = transformPoint4x3(mean, view);
     const float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
     const float txtz = t.x / t.z, tytz = t.y / t.z;
@@ -144,6 +168,7 @@ __device__ __forceinline__ float3 computeCov2D(V3 mean, float focal_x, float foc
     Mat3 T = W * J;
     Mat3 Vrk = mat3_cols(cov3D[0], cov3D[1], cov3D[2], cov3D[1], cov3D[3], cov3D[4], cov3D[2], cov3D[4], cov3D[5]);
     Mat3 cov = transpose(T) * transpose(Vrk) * T;
+    if (raw) *raw = make_float3(cov.m[0][0], cov.m[0][1], cov.m[1][1]);
     cov.m[0][0] += 0.3f;
     cov.m[1][1] += 0.3f;
     return make_float3(cov.m[0][0], cov.m[0][1], cov.m[1][1]);
@@ -281,10 +306,28 @@ __device__ __forceinline__ void cov3D_backward(V3 scale, float mod, float4 rot, 
                 4 * z * (d[1][1] + d[0][0]);
 }
 
-// backward.cu:144-274 for one Gaussian: dL/dconic (a, b, c slots) -> dL/dcov3D (6) and the cov part of dL/dmean
+// backward.cu:215-226: dL/d(a, b, c) of the 2x2 covariance T^t Vrk T -> dL/dcov3D (6)
+__device__ __forceinline__ void cov2D_to_cov3D(const float (*Tq)[3], float dL_da, float dL_db, float dL_dc,
+                                               float dL_dcov[6]) {
+    dL_dcov[0] = (Tq[0][0] * Tq[0][0] * dL_da + Tq[0][0] * Tq[1][0] * dL_db + Tq[1][0] * Tq[1][0] * dL_dc);
+    dL_dcov[3] = (Tq[0][1] * Tq[0][1] * dL_da + Tq[0][1] * Tq[1][1] * dL_db + Tq[1][1] * Tq[1][1] * dL_dc);
+    dL_dcov[5] = (Tq[0][2] * Tq[0][2] * dL_da + Tq[0][2] * Tq[1][2] * dL_db + Tq[1][2] * Tq[1][2] * dL_dc);
+    dL_dcov[1] = 2 * Tq[0][0] * Tq[0][1] * dL_da + (Tq[0][0] * Tq[1][1] + Tq[0][1] * Tq[1][0]) * dL_db +
+                 2 *Tq[1][0] * Tq[1][1] * dL_dc;
+    dL_dcov[2] = 2 * Tq[0][0] * Tq[0][2] * dL_da + (Tq[0][0] * Tq[1][2] + Tq[0][2] * Tq[1][0]) * dL_db +
+                 2 *Tq[1][0] * Tq[1][2] * dL_dc;
+    dL_dcov[4] = 2 * Tq[0][2] * Tq[0][1] * dL_da + (Tq[0][1] * Tq[1][2] + Tq[0][2] * Tq[1][1]) * dL_db +
+                 2 *Tq[1][1] * Tq[1][2] * dL_dc;
+}
+
+// backward.cu:144-274 for one Gaussian: dL/dconic (a, b, c slots) -> dL/dcov3D (6) and the cov part of dL/dmean.
+// AA (the antialiased backward): aa_dL_ds = dL/ds = dL/do_eff * o comes in and *aa_s = s goes out; with
+// dL/dr = dL/ds / (2 s), or 0 for a floored s, the terms dL/dr * (dr/da0, dr/db, dr/dc0) join dL_da, dL_db, dL_dc
+// ahead of the chain to dL/dcov3D and dL/dmean -- also where denom2inv == 0 zeroes the conic's own terms.
+template <bool AA = false>
 __device__ __forceinline__ V3 cov2D_backward(V3 mean, float h_x, float h_y, float tan_fovx, float tan_fovy,
                                              const float cov3D[6], const Mat4 &view, float3 dL_dconic,
-                                             float dL_dcov[6]) {
+                                             float dL_dcov[6], float aa_dL_ds = 0.f, float *aa_s = nullptr) {
     V3 t = transformPoint4x3(mean, view);
     const float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
     const float txtz = t.x / t.z, tytz = t.y / t.z;
@@ -299,6 +342,7 @@ __device__ __forceinline__ V3 cov2D_backward(V3 mean, float h_x, float h_y, floa
     Mat3 Vrk = mat3_cols(cov3D[0], cov3D[1], cov3D[2], cov3D[1], cov3D[3], cov3D[4], cov3D[2], cov3D[4], cov3D[5]);
     Mat3 T = W * J;
     Mat3 cov2D = transpose(T) * transpose(Vrk) * T;
+    const float a0 = cov2D.m[0][0], c0 = cov2D.m[1][1];
     float a = cov2D.m[0][0] += 0.3f;
     float b = cov2D.m[0][1];
     float c = cov2D.m[1][1] += 0.3f;
@@ -310,18 +354,20 @@ __device__ __forceinline__ V3 cov2D_backward(V3 mean, float h_x, float h_y, floa
         dL_da = denom2inv * (-c * c * dL_dconic.x + 2 * b * c * dL_dconic.y + (denom - a * c) * dL_dconic.z);
         dL_dc = denom2inv * (-a * a * dL_dconic.z + 2 * a * b * dL_dconic.y + (denom - a * c) * dL_dconic.x);
         dL_db = denom2inv * 2 * (b * c * dL_dconic.x - (denom + 2 * b * b) * dL_dconic.y + a * b * dL_dconic.z);
-        dL_dcov[0] = (Tq[0][0] * Tq[0][0] * dL_da + Tq[0][0] * Tq[1][0] * dL_db + Tq[1][0] * Tq[1][0] * dL_dc);
-        dL_dcov[3] = (Tq[0][1] * Tq[0][1] * dL_da + Tq[0][1] * Tq[1][1] * dL_db + Tq[1][1] * Tq[1][1] * dL_dc);
-        dL_dcov[5] = (Tq[0][2] * Tq[0][2] * dL_da + Tq[0][2] * Tq[1][2] * dL_db + Tq[1][2] * Tq[1][2] * dL_dc);
-        dL_dcov[1] = 2 * Tq[0][0] * Tq[0][1] * dL_da + (Tq[0][0] * Tq[1][1] + Tq[0][1] * Tq[1][0]) * dL_db +
-                     2 * Tq[1][0] * Tq[1][1] * dL_dc;
-        dL_dcov[2] = 2 * Tq[0][0] * Tq[0][2] * dL_da + (Tq[0][0] * Tq[1][2] + Tq[0][2] * Tq[1][0]) * dL_db +
-                     2 * Tq[1][0] * Tq[1][2] * dL_dc;
-        dL_dcov[4] = 2 * Tq[0][2] * Tq[0][1] * dL_da + (Tq[0][1] * Tq[1][2] + Tq[0][2] * Tq[1][1]) * dL_db +
-                     2 * Tq[1][1] * Tq[1][2] * dL_dc;
-    } else {
+        if (!AA) cov2D_to_cov3D(Tq, dL_da, dL_db, dL_dc, dL_dcov);
+    } else if (!AA) {
 #pragma unroll
         for (int i = 0; i < 6; i++) dL_dcov[i] = 0;
+    }
+    if (AA) {
+        const AAFactor f = aa_factor(a0, b, c0);
+        *aa_s = f.s;
+        const float dL_dr = f.floored ? 0.f : aa_dL_ds / (2.f * f.s);
+        const float D1sq = f.D1 * f.D1;
+        dL_da += dL_dr * ((c0 * f.D1 - f.D0 * c) / D1sq);
+        dL_dc += dL_dr * ((a0 * f.D1 - f.D0 * a) / D1sq);
+        dL_db += dL_dr * (2.f * b * (f.D0 - f.D1) / D1sq);
+        cov2D_to_cov3D(Tq, dL_da, dL_db, dL_dc, dL_dcov);
     }
     const float(*Vq)[3] = Vrk.m;
     float dL_dT00 = 2 * (Tq[0][0] * Vq[0][0] + Tq[0][1] * Vq[0][1] + Tq[0][2] * Vq[0][2]) * dL_da +

@@ -9,6 +9,10 @@ namespace gs4d {
 
 // One thread per Gaussian.  Besides the reference's outputs it produces num_rendered (the sum of
 // tiles_touched, added per workgroup into 8 sharded u64 counters: only the total is ever needed).
+// AA (gs4d_forward_aa's antialiasing): the opacity stored in conic_opacity.w and in the splat record is
+// o_eff = o * s (aa_factor, gs4d_math.h) -- what the exact tile culling, the blend and the render-level gradients
+// read; the conic, the radius and the tile rectangle stay those of the dilated covariance.
+template <bool AA>
 __global__ __launch_bounds__(kPreprocessBlock) void preprocess_kernel(
     Args a, const float *__restrict__ means3D, const float *__restrict__ scales, const float *__restrict__ rotations,
     const float *__restrict__ opacities, const float *__restrict__ shs, const float *__restrict__ cov3D_precomp,
@@ -41,7 +45,8 @@ __global__ __launch_bounds__(kPreprocessBlock) void preprocess_kernel(
 #pragma unroll
                 for (int i = 0; i < 6; i++) g.cov3D[6 * (size_t)idx + i] = cov3[i];
             }
-            cov = computeCov2D(p_orig, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3, view);
+            float3 raw;
+            cov = computeCov2D(p_orig, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3, view, AA ? &raw : nullptr);
             det = (cov.x * cov.z - cov.y * cov.y);
             ok = det != 0.0f;
             if (ok) {
@@ -83,7 +88,9 @@ __global__ __launch_bounds__(kPreprocessBlock) void preprocess_kernel(
                         rgb = make_float3(colors_precomp[3 * idx], colors_precomp[3 * idx + 1],
                                           colors_precomp[3 * idx + 2]);
                     }
-                    const float4 co = make_float4(conic.x, conic.y, conic.z, opacities[idx]);
+                    float opac = opacities[idx];
+                    if (AA) opac = opac * aa_factor(raw.x, raw.y, raw.z).s;
+                    const float4 co = make_float4(conic.x, conic.y, conic.z, opac);
                     g.clamped[idx] = cl;
                     g.depths[idx] = p_view.z;
                     g.xy[idx] = point_image;
@@ -126,10 +133,22 @@ __global__ __launch_bounds__(kPreprocessBlock) void preprocess_kernel(
 
 hipError_t launch_preprocess(const Args &a, const float *means3D, const float *scales, const float *rotations,
                              const float *opacities, const float *shs, const float *cov3D_precomp,
-                             const float *colors_precomp, int *radii, GeomState g, int *err_flag, hipStream_t s) {
+                             const float *colors_precomp, int *radii, GeomState g, int *err_flag, bool antialiasing,
+                             hipStream_t s) {
     const int nblk = (a.P + kPreprocessBlock - 1) / kPreprocessBlock;
-    hipLaunchKernelGGL(preprocess_kernel, dim3(nblk), dim3(kPreprocessBlock), 0, s, a, means3D, scales, rotations,
-                       opacities, shs, cov3D_precomp, colors_precomp, radii, g, err_flag);
+    hipLaunchKernelGGL(antialiasing ? preprocess_kernel<true> : preprocess_kernel<false>, dim3(nblk),
+                       dim3(kPreprocessBlock), 0, s, a, means3D, scales, rotations, opacities, shs, cov3D_precomp,
+                       colors_precomp, radii, g, err_flag);
+    return hipGetLastError();
+}
+
+// gs4d_debug_effective_opacity: out[i] = conic_opacity[i].w of a forward's geometry state
+__global__ void effective_opacity_kernel(int P, const float4 *__restrict__ conic_opacity, float *__restrict__ out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < P) out[idx] = conic_opacity[idx].w;
+}
+hipError_t launch_effective_opacity(int P, GeomState g, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(effective_opacity_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, g.conic_opacity, out);
     return hipGetLastError();
 }
 

@@ -178,13 +178,16 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
 // NV = 10: dL/dmean3D also takes W3 d(p_view.z)/dmean, the view matrix's depth row (forward.cu:250's
 // p_view.z = m[2] x + m[6] y + m[10] z + m[14]); culled Gaussians (radii 0) get nothing.
 // ABS: abs_mean2D of a Gaussian spanning waves comes from the same sum; zeros without instances or with radii 0.
-template <int NV, bool ABS>
+// AA (the antialiased backward; `opacities` = the raw o): the dL_dopacity the reduction left is g = dL/do_eff
+// (conic_opacity.w holds o_eff).  cov2D_backward takes dL/ds = g o into the covariance and returns s, and the
+// stored dL_dopacity becomes dL/do = g s; a Gaussian with radii 0 has no instances and keeps its zero.
+template <int NV, bool ABS, bool AA>
 __device__ __forceinline__ V3 gaussian_grads(
     int idx, const Args &a, const GeomState &g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
     const float *dL_dmean2D, const float4 *dL_dconic, float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscale,
     float *__restrict__ dL_drot, const uint32_t *__restrict__ e_first, const float4 *__restrict__ part,
-    const GradOut &o) {
+    const GradOut &o, const float *__restrict__ opacities) {
     {
         const uint32_t ni = g.n_inst[idx];
         if (ni == 0) {
@@ -213,8 +216,16 @@ __device__ __forceinline__ V3 gaussian_grads(
         for (int i = 0; i < 6; i++) cov3D[i] = cov3Ds[6 * (size_t)idx + i];
         const float4 dc = dL_dconic[idx];
         // K8 (backward.cu:144-274): the covariance part of dL/dmean (assigned, :273)
-        dmean = cov2D_backward(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
-                               make_float3(dc.x, dc.y, dc.w), dcov);
+        if (AA) {
+            const float gop = o.opacity[idx];  // pass 1 or this thread wrote it
+            float s;
+            dmean = cov2D_backward<true>(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
+                                         make_float3(dc.x, dc.y, dc.w), dcov, gop * opacities[idx], &s);
+            o.opacity[idx] = gop * s;
+        } else {
+            dmean = cov2D_backward(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
+                                   make_float3(dc.x, dc.y, dc.w), dcov);
+        }
         // K9 (backward.cu:370-387): projection part
         const float *proj = projm.m;
         const float g2x = dL_dmean2D[3 * idx], g2y = dL_dmean2D[3 * idx + 1];
@@ -249,18 +260,25 @@ __device__ __forceinline__ V3 gaussian_grads(
     return dmean;
 }
 
+// The antialiased instantiations of the two kernels below take one more argument, the raw opacities, as a
+// trailing pack of one; the empty pack leaves the other instantiations' argument lists, and so their code
+// objects, what they were.
+__device__ __forceinline__ const float *raw_opacities() { return nullptr; }
+__device__ __forceinline__ const float *raw_opacities(const float *p) { return p; }
+
 // Without SH coefficients (colours precomputed): one thread per Gaussian, dL/dmean3D = the two terms.
-template <int NV, bool ABS>
+template <int NV, bool ABS, class... Raw>
 __global__ __launch_bounds__(256) void gaussian_backward_kernel(
     Args a, GeomState g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
     const float *dL_dmean2D, const float4 *dL_dconic, float *__restrict__ dL_dmean3D,
     float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscale, float *__restrict__ dL_drot,
-    const uint32_t *__restrict__ e_first, const float4 *__restrict__ part, GradOut o) {
+    const uint32_t *__restrict__ e_first, const float4 *__restrict__ part, GradOut o,
+    Raw... raw) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.P) return;
-    const V3 dmean = gaussian_grads<NV, ABS>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
-                                    dL_dcov3D, dL_dscale, dL_drot, e_first, part, o);
+    const V3 dmean = gaussian_grads<NV, ABS, sizeof...(Raw) != 0>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
+                                    dL_dcov3D, dL_dscale, dL_drot, e_first, part, o, raw_opacities(raw...));
     dL_dmean3D[3 * idx + 0] = dmean.x;
     dL_dmean3D[3 * idx + 1] = dmean.y;
     dL_dmean3D[3 * idx + 2] = dmean.z;
@@ -277,14 +295,15 @@ __global__ __launch_bounds__(256) void gaussian_backward_kernel(
 // work split at the SH part) cost one launch more.
 constexpr int kShThreads = 128, kShRow = 49;
 
-template <bool kVec4, int NV, bool ABS>
+template <bool kVec4, int NV, bool ABS, class... Raw>
 __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     Args a, GeomState g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
     const float *dL_dmean2D, const float4 *dL_dconic, float *__restrict__ dL_dmean3D,
     float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscale, float *__restrict__ dL_drot,
     const uint32_t *__restrict__ e_first, const float4 *__restrict__ part, GradOut o, const float *__restrict__ shs,
-    const uint8_t *__restrict__ clamped, const float *dL_dcolor, float *__restrict__ dL_dsh) {
+    const uint8_t *__restrict__ clamped, const float *dL_dcolor, float *__restrict__ dL_dsh,
+    Raw... raw) {
     __shared__ float tile[kShThreads * kShRow];
     const int g0 = blockIdx.x * kShThreads;
     // rows of M > 16 coefficients: only the first 16 can be used (D <= 3); the rest get zeros
@@ -308,8 +327,9 @@ __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     V3 dmean = v3(0, 0, 0);
     const int idx = g0 + threadIdx.x;
     if ((int)threadIdx.x < n)  // pass 2 writes this Gaussian's dL/dcolor (when it spans waves) before it is read
-        dmean = gaussian_grads<NV, ABS>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic, dL_dcov3D,
-                               dL_dscale, dL_drot, e_first, part, o);
+        dmean = gaussian_grads<NV, ABS, sizeof...(Raw) != 0>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D,
+                                                             dL_dconic, dL_dcov3D, dL_dscale, dL_drot, e_first, part, o,
+                                                             raw_opacities(raw...));
     __syncthreads();
     if ((int)threadIdx.x < n) {
         float *trow = tile + threadIdx.x * kShRow;
@@ -377,24 +397,26 @@ static hipError_t contrib_reduce(const Args &a, GeomState g, BinningState b, int
     return hipGetLastError();
 }
 
-template <int NV, bool ABS>
+template <int NV, bool ABS, class... Raw>
 static hipError_t gaussian_backward(const Args &a, GeomState g, int R, char *scratch, const int *radii,
                                     const float *means3D, const float *shs, const float *scales, const float *rotations,
                                     const float *cov3D, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
                                     float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
-                                    float *dL_dscale, float *dL_drot, float *abs_dmean2D, hipStream_t s) {
+                                    float *dL_dscale, float *dL_drot, float *abs_dmean2D, hipStream_t s, Raw... raw) {
     const GradOut o = grad_out(a, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, abs_dmean2D);
     if (shs) {
         const bool vec4 = a.M == 16 && (((size_t)shs | (size_t)dL_dsh) & 15) == 0;
-        const auto kernel = vec4 ? gaussian_sh_backward_kernel<true, NV, ABS> : gaussian_sh_backward_kernel<false, NV, ABS>;
+        const auto kernel = vec4 ? gaussian_sh_backward_kernel<true, NV, ABS, Raw...>
+                                 : gaussian_sh_backward_kernel<false, NV, ABS, Raw...>;
         hipLaunchKernelGGL(kernel,
                            dim3((a.P + kShThreads - 1) / kShThreads), dim3(kShThreads), 0, s, a, g, radii, means3D,
                            scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot,
-                           scratch_e_first(scratch, R), scratch_part(scratch), o, shs, g.clamped, dL_dcolor, dL_dsh);
+                           scratch_e_first(scratch, R), scratch_part(scratch), o, shs, g.clamped, dL_dcolor, dL_dsh,
+                           raw...);
     } else {
-        hipLaunchKernelGGL((gaussian_backward_kernel<NV, ABS>), dim3((a.P + 255) / 256), dim3(256), 0, s, a, g, radii, means3D,
+        hipLaunchKernelGGL((gaussian_backward_kernel<NV, ABS, Raw...>), dim3((a.P + 255) / 256), dim3(256), 0, s, a, g, radii, means3D,
                            scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dmean3D, dL_dcov3D,
-                           dL_dscale, dL_drot, scratch_e_first(scratch, R), scratch_part(scratch), o);
+                           dL_dscale, dL_drot, scratch_e_first(scratch, R), scratch_part(scratch), o, raw...);
     }
     return hipGetLastError();
 }
@@ -414,11 +436,18 @@ hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scr
                                     const float *rotations, const float *cov3D, float *dL_dmean2D,
                                     float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                                     float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                    float *abs_dmean2D, hipStream_t s) {
+                                    float *abs_dmean2D, const float *opacities, hipStream_t s) {
+    // opacities (the raw ones; NULL for none): the antialiased backward's instantiations
     return with_backward_variant(depth, abs_dmean2D != nullptr, [&](auto depth_c, auto abs_c) {
-        return gaussian_backward<depth_c.value ? 10 : 9, abs_c.value>(
-            a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D, dL_dconic, dL_dopacity,
-            dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, abs_dmean2D, s);
+        constexpr int NV = depth_c.value ? 10 : 9;
+        constexpr bool ABS = abs_c.value;
+        if (opacities)
+            return gaussian_backward<NV, ABS>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
+                                              dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                              dL_drot, abs_dmean2D, s, opacities);
+        return gaussian_backward<NV, ABS>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
+                                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                          dL_drot, abs_dmean2D, s);
     });
 }
 

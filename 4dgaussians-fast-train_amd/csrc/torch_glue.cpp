@@ -67,9 +67,10 @@ torch::Tensor prep_view(const torch::Tensor &t, const torch::Device &dev, int &t
 
 }  // namespace
 
-// rasterize_points.cu:35-117
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
-RasterizeGaussians(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+// rasterize_points.cu:35-117; antialiasing: gs4d_forward_aa's switch (0 = the reference's forward)
+using ForwardTuple = std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+static ForwardTuple
+ForwardImpl(const bool antialiasing, const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
                    const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
                    const float scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
                    const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
@@ -111,17 +112,43 @@ RasterizeGaussians(const torch::Tensor &background, const torch::Tensor &means3D
     Resizer rg{&geomBuffer}, rb{&binningBuffer}, ri{&imgBuffer};
     hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
     int rendered = 0;
-    int st = gs4d_forward_ex(resize_cb, &rg, resize_cb, &rb, resize_cb, &ri, P, degree, M, fptr(bg), W, H, fptr(m3),
+    int st = gs4d_forward_aa(resize_cb, &rg, resize_cb, &rb, resize_cb, &ri, P, degree, M, fptr(bg), W, H, fptr(m3),
                              fptr(shc), fptr(col), fptr(op), fptr(sc), scale_modifier, fptr(rot), fptr(c3), fptr(vm),
                              fptr(pm), fptr(cp), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(),
                              out_depth.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0, (void *)stream,
-                             &rendered, vt);
+                             &rendered, vt, antialiasing ? 1 : 0);
     check_status(st, "rasterize_gaussians");
     return std::make_tuple(rendered, out_color, out_depth, radii, geomBuffer, binningBuffer, imgBuffer);
 }
 
+ForwardTuple
+RasterizeGaussians(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+                   const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+                   const float scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+                   const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
+                   const int image_width, const torch::Tensor &sh, const int degree, const torch::Tensor &campos,
+                   const bool prefiltered, const bool debug) {
+    return ForwardImpl(false, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                       viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                       prefiltered, debug);
+}
+
+// rasterize_gaussians' arguments, then `antialiasing`: gs4d_forward_aa (the opacity blended is o * s)
+ForwardTuple
+RasterizeGaussiansAA(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &colors,
+                     const torch::Tensor &opacity, const torch::Tensor &scales, const torch::Tensor &rotations,
+                     const float scale_modifier, const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+                     const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy,
+                     const int image_height, const int image_width, const torch::Tensor &sh, const int degree,
+                     const torch::Tensor &campos, const bool prefiltered, const bool debug, const bool antialiasing) {
+    return ForwardImpl(antialiasing, background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                       cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
+                       campos, prefiltered, debug);
+}
+
 // rasterize_points.cu:119-198; dL_dout_depth != nullptr: the depth-gradient backward (gs4d_backward_depth);
-// dL_dout_alpha != nullptr: gs4d_backward_aux, where an empty tensor for either image means "no such gradient"
+// dL_dout_alpha != nullptr: gs4d_backward_aux, where an empty tensor for either image means "no such gradient";
+// opacities != nullptr: gs4d_backward_aa (the forward's raw opacities and its `antialiasing`)
 using BackwardTuple = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
                                  torch::Tensor, torch::Tensor, torch::Tensor>;
 static BackwardTuple
@@ -133,7 +160,8 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
                            const float tan_fovy, const torch::Tensor &dL_dout_color, const torch::Tensor &sh,
                            const int degree, const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
                            const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug,
-                           torch::Tensor *abs_out = nullptr) {
+                           torch::Tensor *abs_out = nullptr, const torch::Tensor *opacities = nullptr,
+             const bool antialiasing = false) {
     if (!means3D.is_cuda()) throw std::runtime_error("means3D must be a HIP (GPU) tensor; the MI355X rasterizer has no CPU path");
     const auto dev = means3D.device();
     c10::hip::HIPGuard guard(dev.index());
@@ -196,7 +224,15 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
         const auto call = [&](const char *what, auto entry, auto images, auto abs_ptr) {
             check_status(std::apply(entry, std::tuple_cat(head, images, outs, abs_ptr, tail)), what);
         };
-        if (abs_out)
+        if (opacities) {
+            if (antialiasing && opacities->numel() != P) throw std::runtime_error("opacities must have P elements");
+            auto op = prep(*opacities, "opacities", dev);
+            check_status(std::apply(gs4d_backward_aa,
+                                    std::tuple_cat(head, std::make_tuple(pix, dep, alp), outs,
+                                                   std::make_tuple(abs_out ? abs_out->data_ptr<float>() : (float *)nullptr),
+                                                   tail, std::make_tuple(fptr(op), antialiasing ? 1 : 0))),
+                         "rasterize_gaussians_backward_aa");
+        } else if (abs_out)
             call("rasterize_gaussians_backward_absgrad", gs4d_backward_absgrad, std::make_tuple(pix, dep, alp),
                  std::make_tuple(abs_out->data_ptr<float>()));
         else if (dL_dout_alpha)
@@ -276,6 +312,42 @@ RasterizeGaussiansBackwardAbsgrad(const torch::Tensor &background, const torch::
                           scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                           degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, &absgrad);
     return std::tuple_cat(std::move(t), std::make_tuple(absgrad));
+}
+
+// rasterize_gaussians_backward_absgrad's arguments, then the forward's opacities, its `antialiasing` and `absgrad`
+// (false: the ninth tensor of the tuple comes back empty): gs4d_backward_aa, one entry for every combination
+AbsgradTuple
+RasterizeGaussiansBackwardAA(const torch::Tensor &background, const torch::Tensor &means3D, const torch::Tensor &radii,
+                             const torch::Tensor &colors, const torch::Tensor &scales, const torch::Tensor &rotations,
+                             const float scale_modifier, const torch::Tensor &cov3D_precomp,
+                             const torch::Tensor &viewmatrix, const torch::Tensor &projmatrix, const float tan_fovx,
+                             const float tan_fovy, const torch::Tensor &dL_dout_color,
+                             const torch::Tensor &dL_dout_depth, const torch::Tensor &dL_dout_alpha,
+                             const torch::Tensor &sh, const int degree, const torch::Tensor &campos,
+                             const torch::Tensor &geomBuffer, const int R, const torch::Tensor &binningBuffer,
+                             const torch::Tensor &imageBuffer, const bool debug, const torch::Tensor &opacities,
+                             const bool antialiasing, const bool absgrad) {
+    torch::Tensor abs = torch::empty({0}, means3D.options().dtype(torch::kFloat32));
+    auto t = BackwardImpl(&dL_dout_depth, &dL_dout_alpha, background, means3D, radii, colors, scales, rotations,
+                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                          degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, absgrad ? &abs : nullptr,
+                          &opacities, antialiasing);
+    return std::tuple_cat(std::move(t), std::make_tuple(abs));
+}
+
+// conic_opacity.w of the forward that filled geomBuffer, (P,): gs4d_debug_effective_opacity
+torch::Tensor DebugEffectiveOpacity(const torch::Tensor &geomBuffer, const int P) {
+    TORCH_CHECK(geomBuffer.is_cuda() && geomBuffer.scalar_type() == torch::kByte && P >= 0,
+                "debug_effective_opacity: the geometry state of a forward over P Gaussians");
+    const c10::hip::HIPGuard guard(geomBuffer.device().index());
+    torch::Tensor out = torch::empty({P}, geomBuffer.options().dtype(torch::kFloat32));
+    if (P == 0) return out;
+    TORCH_CHECK(geomBuffer.numel() >= 64LL * P, "debug_effective_opacity: geomBuffer is too small for P Gaussians");
+    check_status(gs4d_debug_effective_opacity(P, reinterpret_cast<const char *>(geomBuffer.data_ptr()),
+                                              out.data_ptr<float>(),
+                                              (void *)c10::hip::getCurrentHIPStream(geomBuffer.device().index()).stream()),
+                 "debug_effective_opacity");
+    return out;
 }
 
 // the alpha image 1 - T_final (1, H, W) of the forward that filled imageBuffer: gs4d_alpha_image
@@ -377,6 +449,9 @@ PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);
     m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux);
     m.def("rasterize_gaussians_backward_absgrad", &RasterizeGaussiansBackwardAbsgrad);
+    m.def("rasterize_gaussians_aa", &RasterizeGaussiansAA);
+    m.def("rasterize_gaussians_backward_aa", &RasterizeGaussiansBackwardAA);
+    m.def("debug_effective_opacity", &DebugEffectiveOpacity);
     m.def("alpha_image", &AlphaImage);
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });

@@ -14,7 +14,10 @@ also back-propagates the depth image's gradient, which the reference drops (:100
 _RasterizeGaussiansAux, which also returns the accumulated-alpha image 1 - T_final (1, H, W) as a fourth,
 differentiable output (the reference returns no such image, :98); absgrad=True selects the _RasterizeGaussians*Abs
 Functions, whose backward also leaves the absolute screen-space gradient (AbsGS; gsplat's `absgrad`) in
-`means2D.absgrad`, a (P, 3) tensor overwritten by every backward call.  The compute runs in libgs4d (HIP
+`means2D.absgrad`, a (P, 3) tensor overwritten by every backward call.  A fourth, antialiasing=True, is a value
+of the forward and not another Function: the opacity blended is o * sqrt(max(2.5e-5, det S / det(S + 0.3 I))) for
+the projected covariance S (Mip-Splatting's 2-D filter; gsplat's rasterize_mode="antialiased"), and the backward
+carries that factor's gradient into the covariance; radii and the binning do not change.  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
 without the built extension raises ImportError -- there is no CPU fallback.
 """
@@ -65,11 +68,15 @@ def _invoke(fn, args, debug, dump_name, stage):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_grad=False, alpha=False, absgrad=False):
+                        raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False):
     """(color, radii, depth), or with alpha=True (color, radii, depth, alpha).  absgrad=True: the backward also
     assigns `means2D.absgrad` (P, 3): per Gaussian the sum over its pixels of |the pixel's term of means2D.grad|
-    in x and y (column 2 is 0), where means2D.grad holds the signed sum."""
+    in x and y (column 2 is 0), where means2D.grad holds the signed sum.  antialiasing=True: the footprint-
+    compensated opacity (module docstring) is blended, through the same Function."""
     fn = _FUNCTIONS[bool(depth_grad), bool(alpha), bool(absgrad)]
+    if antialiasing:
+        return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                        raster_settings, True)
     return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                     raster_settings)
 
@@ -79,15 +86,20 @@ def _zero_image(channels, s, like):
 
 
 def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-             raster_settings):
+             raster_settings, antialiasing=False):
     depth_grad, alpha, absgrad = variant
     s = raster_settings
     # positional order of _C.rasterize_gaussians (rasterize_points.h:18-38)
     args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
             s.campos, s.prefiltered, s.debug)
-    num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
-        _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
+    if antialiasing:  # the same arguments, then the switch; the backward needs the raw opacities
+        num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
+            _C.rasterize_gaussians_aa, args + (True,), s.debug, "snapshot_fw.dump", "forward")
+    else:
+        num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
+            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
+    ctx.antialiasing = bool(antialiasing)
     ctx.variant = variant
     ctx.raster_settings = s
     ctx.num_rendered = num_rendered
@@ -96,7 +108,7 @@ def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scal
     ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf,
-                          binning_buf, img_buf)
+                          binning_buf, img_buf, *((opacities,) if antialiasing else ()))
     if absgrad:
         ctx.absgrad_target = means2D  # the caller's tensor: the backward assigns its .absgrad
     if not alpha:
@@ -113,12 +125,21 @@ def _backward(ctx, grad_out_color, grad_depth, grad_alpha):
     s = ctx.raster_settings
     if not depth_grad:  # no gradient flows from the depth image, exactly like the reference (:100-101)
         grad_depth = None
+    extra = (None,) if ctx.antialiasing else ()  # the switch itself, when it was an input
     if grad_out_color is None and grad_depth is None and grad_alpha is None:
-        return (None,) * 9  # only images without a gradient path were used: nothing flows back
+        return (None,) * 9 + extra  # only images without a gradient path were used: nothing flows back
     (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
-     img_buf) = ctx.saved_tensors
+     img_buf) = ctx.saved_tensors[:10]
     # the entry and its upstream images, which follow grad_out_color in its argument list
-    if alpha or absgrad:  # an empty tensor stands for "no such gradient"
+    tail = ()
+    if ctx.antialiasing:  # one entry for every combination: empty tensors and absgrad=False stand for "off"
+        entry = _C.rasterize_gaussians_backward_aa
+        if grad_out_color is None:
+            grad_out_color = _zero_image(3, s, means3D)
+        none = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        grads = (grad_out_color, none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha)
+        tail = (ctx.saved_tensors[10], True, bool(absgrad))
+    elif alpha or absgrad:  # an empty tensor stands for "no such gradient"
         entry = _C.rasterize_gaussians_backward_absgrad if absgrad else _C.rasterize_gaussians_backward_aux
         if grad_out_color is None:
             grad_out_color = _zero_image(3, s, means3D)
@@ -137,12 +158,12 @@ def _backward(ctx, grad_out_color, grad_depth, grad_alpha):
     # positional order of _C.rasterize_gaussians_backward (rasterize_points.h:40-62)
     args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, *grads, sh, s.sh_degree, s.campos,
-            geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug)
+            geom_buf, ctx.num_rendered, binning_buf, img_buf, s.debug, *tail)
     out = _invoke(entry, args, s.debug, "snapshot_bw.dump", "backward")
     if absgrad:
         ctx.absgrad_target.absgrad = out[8]  # overwritten per backward call (gsplat's convention)
     g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations = out[:8]
-    return g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None
+    return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None) + extra
 
 
 def _variant(depth_grad, alpha, absgrad):
@@ -211,8 +232,9 @@ def _empty_if_none(t):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings, depth_grad=False, alpha=False, absgrad=False):
+    def __init__(self, raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False):
         super().__init__()
+        self.antialiasing = antialiasing  # opt-in: the footprint-compensated opacity o * s is blended
         self.absgrad = absgrad  # opt-in: the backward assigns means2D.absgrad (_RasterizeGaussians*Abs)
         self.raster_settings = raster_settings
         self.depth_grad = depth_grad  # opt-in: the depth image's gradient flows back (_RasterizeGaussiansDepth)
@@ -235,4 +257,4 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, _empty_if_none(shs), _empty_if_none(colors_precomp), opacities,
                                    _empty_if_none(scales), _empty_if_none(rotations), _empty_if_none(cov3D_precomp),
                                    self.raster_settings, depth_grad=self.depth_grad, alpha=self.alpha,
-                                   absgrad=self.absgrad)
+                                   absgrad=self.absgrad, antialiasing=self.antialiasing)

@@ -38,7 +38,10 @@ def optimization_params(**over):
              # opt-in (AbsGS): densify on the absolute screen-space gradient, sum over pixels of |per-pixel term|, in
              # place of the norm of the signed sum (train.py).  The thresholds stay the user's: AbsGS roughly doubles
              # densify_grad_threshold_* (0.0004 where the signed gradient uses 0.0002)
-             densify_absgrad=False)
+             densify_absgrad=False,
+             # opt-in (Mip-Splatting's 2-D filter): every view is rendered with antialiasing=True, the
+             # footprint-compensated opacity (train.py); render the trained model with the same value
+             antialiasing=False)
     d.update(over)
     return SimpleNamespace(**d)
 

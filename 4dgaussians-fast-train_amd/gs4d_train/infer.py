@@ -151,8 +151,9 @@ def get_state_at_time(state, camera):
 
 
 @torch.no_grad()
-def render_view(camera, state, bg, scaling_modifier=1.0):
-    """render()'s dict (gaussian_renderer/__init__.py:130-138) for a captured model, through the same rasterizer."""
+def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False):
+    """render()'s dict (gaussian_renderer/__init__.py:130-138) for a captured model, through the same rasterizer.
+    antialiasing: render()'s switch; a model trained with it on is rendered with it on."""
     import diff_gaussian_rasterization as dgr
     dev = state.xyz.device
     if hasattr(camera, "on_device"):
@@ -166,7 +167,7 @@ def render_view(camera, state, bg, scaling_modifier=1.0):
         scale_modifier=scaling_modifier, viewmatrix=view_m, projmatrix=proj_m, sh_degree=state.active_sh_degree,
         campos=cam_c, prefiltered=False, debug=False)
     m3, sc, rot, op, sh = state_at_time(state, camera.time, activate=True)
-    image, radii, depth = dgr.GaussianRasterizer(raster_settings=settings)(
+    image, radii, depth = dgr.GaussianRasterizer(raster_settings=settings, antialiasing=antialiasing)(
         means3D=m3, means2D=state.zero_points, shs=sh, colors_precomp=None, opacities=op, scales=sc, rotations=rot,
         cov3D_precomp=None)
     return {"render": image, "viewspace_points": state.zero_points, "visibility_filter": radii > 0, "radii": radii,
@@ -178,14 +179,15 @@ def _sync(state):
         torch.cuda.synchronize(state.xyz.device)
 
 
-def render_set(state, cameras, bg, keep_images=True):
+def render_set(state, cameras, bg, keep_images=True, antialiasing=False):
     """(images, fps): every camera rendered in order, and the reference's frame rate (render.py:57-70),
     (len(cameras) - 1) / (t_end - t_after_first) with the device synchronised before each clock read (nan for
-    fewer than two cameras).  keep_images=False drops each image once rendered (images is then empty)."""
+    fewer than two cameras).  keep_images=False drops each image once rendered (images is then empty).
+    antialiasing: render_view's."""
     images = []
     n, t1 = 0, 0.0
     for cam in cameras:
-        img = render_view(cam, state, bg)["render"]
+        img = render_view(cam, state, bg, antialiasing=antialiasing)["render"]
         if keep_images:
             images.append(img)
         n += 1
@@ -198,13 +200,13 @@ def render_set(state, cameras, bg, keep_images=True):
     return images, fps
 
 
-def evaluate(state, views, bg):
+def evaluate(state, views, bg, antialiasing=False):
     """{"psnr", "ssim"}: the means over `views` -- (camera, ground truth (3, H, W)) pairs -- of each image's PSNR
-    and SSIM, as metrics.py forms them; the rendering is clamped to [0, 1]."""
+    and SSIM, as metrics.py forms them; the rendering is clamped to [0, 1].  antialiasing: render_view's."""
     from .losses import psnr
     vp, vs = [], []
     for cam, gt in views:
-        img = render_view(cam, state, bg)["render"].clamp(0, 1).unsqueeze(0)
+        img = render_view(cam, state, bg, antialiasing=antialiasing)["render"].clamp(0, 1).unsqueeze(0)
         gt = gt.to(img.device).unsqueeze(0)
         if img.is_cuda:
             from .kernels import ssim

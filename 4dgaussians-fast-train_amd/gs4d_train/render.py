@@ -101,8 +101,10 @@ class RenderPackage(dict):
 
 
 def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False,
-           alpha=False, absgrad=False):
-    """absgrad=True (opt-in): after the backward, `viewspace_points.absgrad` (P, 3) holds the absolute screen-space
+           alpha=False, absgrad=False, antialiasing=False):
+    """antialiasing=True (opt-in): the rasterizer blends the footprint-compensated opacity o * s (Mip-Splatting's 2-D
+    filter) and its backward carries s's gradient into the covariance; render a model with the value it was trained
+    with.  absgrad=True (opt-in): after the backward, `viewspace_points.absgrad` (P, 3) holds the absolute screen-space
     gradient, the sum over pixels of |each pixel's term of viewspace_points.grad| (AbsGS), overwritten per backward.
     depth_grad=True (this build's opt-in): the gradient of the returned "depth" flows back through the
     rasterizer; by default it is dropped, as in the reference.  alpha=True (opt-in as well): the package gains
@@ -126,7 +128,7 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
     # over the P rows (made once per (device, time); no fill per call)
     time = _time_value(_time_float(viewpoint_camera.time), dev).expand(xyz.shape[0], 1)
     rasterizer = dgr.GaussianRasterizer(raster_settings=settings, depth_grad=depth_grad, alpha=alpha,
-                                        absgrad=absgrad)
+                                        absgrad=absgrad, antialiasing=antialiasing)
     if "coarse" not in stage and "fine" not in stage:
         raise NotImplementedError(stage)
     if getattr(pc, "fused", False) and getattr(pc, "fused_tail", True) and xyz.is_cuda:

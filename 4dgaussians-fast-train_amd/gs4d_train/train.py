@@ -25,6 +25,10 @@ and the densification statistics accumulate the norm of the views' summed `views
 per Gaussian the sum over its pixels of |the pixel's pull on the 2-D mean| -- in place of the norm of the signed
 sum `viewspace_points.grad`, which cancels for a large blurry Gaussian pulled both ways.  The thresholds are the
 user's: AbsGS roughly doubles densify_grad_threshold_* (0.0004 for the reference's 0.0002).
+
+Antialiased rasterization (opt-in, Mip-Splatting's 2-D filter): with opt.antialiasing every view is rendered with
+antialiasing=True, the opacity compensated for the rasterizer's 0.3 px^2 low-pass; a model trained so is rendered
+so (infer.render_view / render_set / evaluate take the same switch).
 """
 import functools
 
@@ -53,7 +57,8 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     render_fn(camera, gaussians, debug, bg, stage=...) -> render()'s dict; defaults to
     gs4d_train.render.render (the HIP rasterizer).  The multi-process CPU tests pass a torch stand-in.  It is
     called with depth_grad=True and / or alpha=True only for the views that need them, and with absgrad=True for
-    every view when opt.densify_absgrad is on (its viewspace_points must then carry .absgrad after the backward)."""
+    every view when opt.densify_absgrad is on (its viewspace_points must then carry .absgrad after the backward),
+    and with antialiasing=True for every view when opt.antialiasing is on."""
     if render_fn is None:
         from .render import render as render_fn
     fused = gaussians.fused if fused_loss is None else fused_loss
@@ -69,6 +74,8 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     densify_absgrad = bool(getattr(opt, "densify_absgrad", False))
     if densify_absgrad:
         render_fn = functools.partial(render_fn, absgrad=True)
+    if bool(getattr(opt, "antialiasing", False)):
+        render_fn = functools.partial(render_fn, antialiasing=True)
     for v in mine:
         cam, gt = views[v][0], views[v][1]
         has_depth = lambda_depth != 0 and len(views[v]) > 2 and views[v][2] is not None

@@ -181,6 +181,50 @@ int gs4d_backward_absgrad(int P, int D, int M, int R, const float *background, i
                           gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream,
                           int view_transposed);
 
+/* Antialiased rasterization (Mip-Splatting's 2-D filter; the `antialiasing` switch of the current Inria
+ * rasterizer, gsplat's rasterize_mode="antialiased"; no reference counterpart; opt-in).  The forward dilates every
+ * projected covariance by 0.3 px^2 (forward.cu:110-111) and leaves the opacity, so a splat below a pixel deposits
+ * more energy than it holds.  With (a0, b, c0) the projected covariance before the low-pass, a = a0 + 0.3,
+ * c = c0 + 0.3:
+ *     D0 = a0 c0 - b^2    D1 = a c - b^2    r = D0 / D1    s = sqrt(max(2.5e-5, r))    o_eff = o s
+ * gs4d_forward_aa is gs4d_forward_ex plus `antialiasing`: non-zero blends with o_eff in place of o.  What changes:
+ * the opacity the exact tile culling, the blend and (later) the render-level gradients read.  What does not: the
+ * conic, radii, the tile rectangles and *num_rendered, which stay those of the dilated covariance.
+ * antialiasing = 0 gives gs4d_forward_ex's bits. */
+int gs4d_forward_aa(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
+                    gs4d_alloc_fn image_alloc, void *image_ctx, int P, int D, int M, const float *background,
+                    int width, int height, const float *means3D, const float *shs, const float *colors_precomp,
+                    const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+                    const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix,
+                    const float *cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float *out_color,
+                    float *out_depth, int *radii, int debug, void *stream, int *num_rendered, int view_transposed,
+                    int antialiasing);
+
+/* The backward of gs4d_forward_aa: gs4d_backward_absgrad's arguments, then the forward's `opacities` (P floats, the
+ * raw o) and `antialiasing`.  dL_ddepth, dL_dalpha and abs_dmean2D may each be NULL ("off"), so the one entry
+ * serves every combination of the opt-ins.  With antialiasing != 0 (the matching forward's value) and
+ * g = dL/do_eff, what the other entries return as dL_dopacity:
+ *     dL_dopacity = g s        dL/ds = g o        dL/dr = r <= 2.5e-5 ? 0 : dL/ds / (2 s)
+ *     dr/da0 = (c0 D1 - D0 c) / D1^2    dr/dc0 = (a0 D1 - D0 a) / D1^2    dr/db = 2 b (D0 - D1) / D1^2
+ * and dL/dr times these joins the conic's gradient with respect to (a, b, c) (backward.cu:196-208) ahead of the chain
+ * to dL_dcov3D (hence dL_dscale, dL_drot) and the covariance part of dL_dmean3D -- also where the reference's
+ * denom2inv == 0 zeroes the conic's own terms.  The floor is a constant of the backward, and the forward and the
+ * backward decide it by the same arithmetic.  dL_dmean2D, dL_dcolor, dL_dsh and abs_dmean2D are what the other
+ * entries give for a plain forward whose opacities are o_eff.  antialiasing = 0 gives the bits of
+ * gs4d_backward_ex / _depth / _aux / _absgrad for the same pointers; `opacities` is then not read.
+ * Status as gs4d_backward_aux (GS4D_OK at once for P == 0), and GS4D_ERR_ARG for NULL `opacities` with
+ * antialiasing != 0. */
+int gs4d_backward_aa(int P, int D, int M, int R, const float *background, int width, int height,
+                     const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                     float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                     const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                     float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                     const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
+                     float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                     float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D, gs4d_alloc_fn scratch_alloc,
+                     void *scratch_ctx, int debug, void *stream, int view_transposed, const float *opacities,
+                     int antialiasing);
+
 /* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.
@@ -221,6 +265,12 @@ int gs4d_voxel_downsample(int N, const float *points, const float *colors, doubl
  * a width x height image).  gid/px/py: n int32 device arrays; og/pw: n fp32 device outputs. */
 int gs4d_debug_pair_alpha(int P, int width, int height, const char *geometry_buffer, int n, const int *gid,
                           const int *px, const int *py, float *og, float *pw, void *stream);
+
+/* Diagnostic for the antialiasing tests (no reference counterpart): out[i] = the opacity the blend reads for
+ * Gaussian i (conic_opacity.w of the geometry state a forward over P Gaussians left in geometry_buffer): o after a
+ * plain forward, o_eff = o s after gs4d_forward_aa with antialiasing.  out: P floats on the device.  Rows of
+ * Gaussians the forward culled (radii == 0) are unspecified.  GS4D_ERR_ARG for P < 0 or a NULL pointer with P > 0. */
+int gs4d_debug_effective_opacity(int P, const char *geometry_buffer, float *out, void *stream);
 
 /* Diagnostic for the blend backward's pair reduction (no reference counterpart): n pairs of splats, one wave
  * each, reduce given per-lane partial sums to their two 12-float records, once as the blend kernel does (column

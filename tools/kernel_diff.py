@@ -1,13 +1,15 @@
 """Compare the kernels of two sets of gfx950 code objects byte for byte (no GPU needed).
 
-  python tools/kernel_diff.py --a <old ELF> [...] --b <new ELF> [...]
+  python tools/kernel_diff.py --a <old ELF> [...] --b <new ELF> [...] [--rename OLD=NEW ...]
 
 Each ELF is a device-only, unbundled code object: a source compiled with the flags build_ext.py gives it plus
 `--cuda-device-only --no-gpu-bundle-output -c`.  A kernel is a function symbol <name> with a descriptor
 symbol <name>.kd; per kernel name the tool compares the function's bytes in .text and the 64-byte descriptor
 (registers, LDS, scratch, ...).  The descriptor's bytes 16..23 are the distance from the descriptor to the
 code, a property of the file's layout and not of the kernel: they are checked to point at the function and
-left out of the comparison.  Prints the kernels that are identical, that differ and that only one side has;
+left out of the comparison.  `--rename OLD=NEW` compares the old side's kernels whose names begin with OLD with the
+new side's whose names begin with NEW (a kernel that became a template instantiation keeps its code and its
+descriptor and changes its name).  Prints the kernels that are identical, that differ and that only one side has;
 the exit status is 1 when a kernel differs (or an ELF cannot be read), else 0.
 """
 import argparse
@@ -84,8 +86,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--a", nargs="+", required=True, help="code objects of the old side")
     ap.add_argument("--b", nargs="+", required=True, help="code objects of the new side")
+    ap.add_argument("--rename", nargs="*", default=[], metavar="OLD=NEW",
+                    help="a kernel whose name begins with OLD on the old side is compared with the one whose name "
+                         "has NEW there on the new side (a kernel that became a template instantiation)")
     args = ap.parse_args()
     a, b = gather(args.a), gather(args.b)
+    for pair in args.rename:
+        old, new = pair.split("=", 1)
+        b = {(old + n[len(new):] if n.startswith(new) else n): k for n, k in b.items()}
     names = sorted(set(a) | set(b))
     same = [n for n in names if n in a and n in b and a[n] == b[n]]
     differ = [n for n in names if n in a and n in b and a[n] != b[n]]

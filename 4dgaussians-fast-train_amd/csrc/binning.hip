@@ -835,4 +835,28 @@ hipError_t launch_binning(const Args &a, GeomState g, const int *radii, BinningS
     return hipGetLastError();
 }
 
+// gs4d_debug_tile_lists: the sorted lists of a finished forward, read back for the tests (read-only).  A slot or an
+// id out of range (buffers of another forward) is reported as gid = ~0 instead of being followed.
+__global__ void tile_lists_kernel(int P, int L, const uint32_t *__restrict__ n_dev, const uint32_t *__restrict__ upos,
+                                  const uint32_t *__restrict__ gid_by_e, const float *__restrict__ depths,
+                                  uint32_t *__restrict__ gid, uint32_t *__restrict__ reach,
+                                  uint32_t *__restrict__ slot, float *__restrict__ depth) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= min(*n_dev, (uint32_t)L)) return;
+    const uint32_t e = upos[i];
+    const uint32_t v = e < (uint32_t)L ? gid_by_e[e] : ~0u;
+    const uint32_t id = v & kGidMask;
+    const bool ok = e < (uint32_t)L && id < (uint32_t)P;
+    slot[i] = e;
+    gid[i] = ok ? id : ~0u;
+    reach[i] = ok ? v >> kReachShift : 0u;
+    depth[i] = ok ? depths[id] : 0.f;
+}
+hipError_t launch_tile_lists(int P, int L, GeomState g, BinningState b, uint32_t *gid, uint32_t *reach,
+                             uint32_t *slot, float *depth, hipStream_t s) {
+    hipLaunchKernelGGL(tile_lists_kernel, dim3((L + 255) / 256), dim3(256), 0, s, P, L, b.scratch, b.upos, b.gid_by_e,
+                       g.depths, gid, reach, slot, depth);
+    return hipGetLastError();
+}
+
 }  // namespace gs4d

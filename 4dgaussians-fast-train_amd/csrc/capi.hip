@@ -254,6 +254,31 @@ int gs4d_debug_effective_opacity(int P, const char *geometry_buffer, float *out,
     return GS4D_OK;
 }
 
+int gs4d_debug_tile_lists(int P, int width, int height, int num_rendered, const char *geometry_buffer,
+                          const char *binning_buffer, const char *image_buffer, uint32_t *ranges, uint32_t *order,
+                          uint32_t *n_emitted, uint32_t *gid, uint32_t *reach, uint32_t *slot, float *depth,
+                          void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int R = num_rendered;
+    if (P <= 0 || width <= 0 || height <= 0 || R < 0 || !geometry_buffer || !image_buffer || !ranges || !order ||
+        !n_emitted || (R > 0 && (!binning_buffer || !gid || !reach || !slot || !depth)))
+        return fail(GS4D_ERR_ARG, "debug_tile_lists: bad args");
+    // the three states as backward_impl carves them
+    const int T = ((width + kBlockX - 1) / kBlockX) * ((height + kBlockY - 1) / kBlockY);
+    GeomState g = GeomState::carve(const_cast<char *>(geometry_buffer), P, T);
+    ImageState img = ImageState::carve(const_cast<char *>(image_buffer), width, height);
+    GS4D_HIP(hipMemcpyAsync(ranges, img.ranges, sizeof(uint2) * (size_t)T, hipMemcpyDeviceToDevice, stream));
+    GS4D_HIP(hipMemcpyAsync(order, img.order, 4 * (size_t)T, hipMemcpyDeviceToDevice, stream));
+    if (R == 0) {  // no emission ran: the binning state holds no L'
+        GS4D_HIP(hipMemsetAsync(n_emitted, 0, 4, stream));
+        return GS4D_OK;
+    }
+    BinningState b = BinningState::carve(const_cast<char *>(binning_buffer), R, T);
+    GS4D_HIP(hipMemcpyAsync(n_emitted, b.scratch, 4, hipMemcpyDeviceToDevice, stream));
+    GS4D_HIP(launch_tile_lists(P, R, g, b, gid, reach, slot, depth, stream));
+    return GS4D_OK;
+}
+
 int gs4d_forward_aa(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
                     gs4d_alloc_fn image_alloc, void *image_ctx, int P, int D, int M, const float *background,
                     int width, int height, const float *means3D, const float *shs, const float *colors_precomp,

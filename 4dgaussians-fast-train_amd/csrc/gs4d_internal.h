@@ -201,6 +201,10 @@ hipError_t launch_mark_visible(int P, const float *means3D, const float *viewmat
 hipError_t launch_visible_scan(const Args &a, GeomState g, hipStream_t s);
 hipError_t launch_binning(const Args &a, GeomState g, const int *radii, BinningState b, int L, ImageState img,
                           hipStream_t s);
+// gs4d_debug_tile_lists: the lists of a finished forward in render order, position i < min(L', L): gid[i] =
+// gid_by_e[upos[i]] & kGidMask, reach[i] its half-reach bits, slot[i] = upos[i], depth[i] = depths[gid[i]]
+hipError_t launch_tile_lists(int P, int L, GeomState g, BinningState b, uint32_t *gid, uint32_t *reach,
+                             uint32_t *slot, float *depth, hipStream_t s);
 hipError_t launch_render_forward(const Args &a, GeomState g, BinningState b, ImageState img, float *out_color,
                                  float *out_depth, hipStream_t s);  // also sorts runs <= kWaveSortMax
 hipError_t launch_pair_alpha(GeomState g, int n, const int *gid, const int *px, const int *py, float *og, float *pw,

@@ -11,6 +11,7 @@
 #include <c10/hip/HIPGuard.h>
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <tuple>
@@ -350,6 +351,43 @@ torch::Tensor DebugEffectiveOpacity(const torch::Tensor &geomBuffer, const int P
     return out;
 }
 
+// the per-tile instance lists of the forward that filled the three buffers, in render order: gs4d_debug_tile_lists.
+// Returns (ranges (T, 2), order (T,), L', gid (L',), reach (L',), slot (L',), depth (L',)): int32 but the fp32 depth
+std::tuple<torch::Tensor, torch::Tensor, int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+DebugTileLists(const torch::Tensor &geomBuffer, const torch::Tensor &binningBuffer, const torch::Tensor &imgBuffer,
+               const int P, const int W, const int H, const int num_rendered) {
+    TORCH_CHECK(geomBuffer.is_cuda() && imgBuffer.is_cuda() && geomBuffer.scalar_type() == torch::kByte &&
+                    imgBuffer.scalar_type() == torch::kByte && binningBuffer.scalar_type() == torch::kByte &&
+                    P > 0 && W > 0 && H > 0 && num_rendered >= 0,
+                "debug_tile_lists: the three states of a forward over P > 0 Gaussians and a W x H image");
+    TORCH_CHECK(num_rendered == 0 || (binningBuffer.is_cuda() && binningBuffer.device() == geomBuffer.device()),
+                "debug_tile_lists: binningBuffer must be on the geometry state's device");
+    TORCH_CHECK(imgBuffer.device() == geomBuffer.device(), "debug_tile_lists: buffers on different devices");
+    const long long T = (long long)((W + 15) / 16) * ((H + 15) / 16);
+    TORCH_CHECK(geomBuffer.numel() >= 64LL * P, "debug_tile_lists: geomBuffer is too small for P Gaussians");
+    TORCH_CHECK(imgBuffer.numel() >= 8LL * W * H + 12 * T, "debug_tile_lists: imgBuffer is not a W x H image state");
+    TORCH_CHECK(binningBuffer.numel() >= 20LL * num_rendered,
+                "debug_tile_lists: binningBuffer is too small for num_rendered instances");
+    const c10::hip::HIPGuard guard(geomBuffer.device().index());
+    const auto iopts = geomBuffer.options().dtype(torch::kInt32);
+    torch::Tensor ranges = torch::empty({T, 2}, iopts), order = torch::empty({T}, iopts);
+    torch::Tensor n = torch::empty({1}, iopts);
+    torch::Tensor gid = torch::empty({num_rendered}, iopts), reach = torch::empty({num_rendered}, iopts),
+                  slot = torch::empty({num_rendered}, iopts);
+    torch::Tensor depth = torch::empty({num_rendered}, geomBuffer.options().dtype(torch::kFloat32));
+    const auto u32 = [](torch::Tensor &t) { return t.numel() ? reinterpret_cast<uint32_t *>(t.data_ptr<int>()) : nullptr; };
+    check_status(gs4d_debug_tile_lists(P, W, H, num_rendered, reinterpret_cast<const char *>(geomBuffer.data_ptr()),
+                                       num_rendered ? reinterpret_cast<const char *>(binningBuffer.data_ptr()) : nullptr,
+                                       reinterpret_cast<const char *>(imgBuffer.data_ptr()), u32(ranges), u32(order),
+                                       u32(n), u32(gid), u32(reach), u32(slot),
+                                       depth.numel() ? depth.data_ptr<float>() : nullptr,
+                                       (void *)c10::hip::getCurrentHIPStream(geomBuffer.device().index()).stream()),
+                 "debug_tile_lists");
+    const int L = std::min(std::max(n.item<int>(), 0), num_rendered);
+    return std::make_tuple(ranges, order, L, gid.slice(0, 0, L), reach.slice(0, 0, L), slot.slice(0, 0, L),
+                           depth.slice(0, 0, L));
+}
+
 // the alpha image 1 - T_final (1, H, W) of the forward that filled imageBuffer: gs4d_alpha_image
 torch::Tensor AlphaImage(const torch::Tensor &imageBuffer, const int image_height, const int image_width) {
     if (!imageBuffer.is_cuda())
@@ -452,6 +490,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians_aa", &RasterizeGaussiansAA);
     m.def("rasterize_gaussians_backward_aa", &RasterizeGaussiansBackwardAA);
     m.def("debug_effective_opacity", &DebugEffectiveOpacity);
+    m.def("debug_tile_lists", &DebugTileLists);
     m.def("alpha_image", &AlphaImage);
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });

@@ -272,6 +272,25 @@ int gs4d_debug_pair_alpha(int P, int width, int height, const char *geometry_buf
  * Gaussians the forward culled (radii == 0) are unspecified.  GS4D_ERR_ARG for P < 0 or a NULL pointer with P > 0. */
 int gs4d_debug_effective_opacity(int P, const char *geometry_buffer, float *out, void *stream);
 
+/* Diagnostic for the tile-list tests (no reference counterpart; read-only): the per-tile instance lists a finished
+ * gs4d_forward over P > 0 Gaussians and a width x height image left in its three buffers, in render order (by tile,
+ * then depth bits, then Gaussian id).  The buffers are carved exactly as gs4d_backward carves them, num_rendered being
+ * the forward's.  With T = ceil(width / 16) * ceil(height / 16) tiles, all outputs on the device:
+ *   ranges     2 T uint32: tile t's list is positions [ranges[2 t], ranges[2 t + 1]); an empty tile has (0, 0)
+ *   order      T uint32: the blend kernels' workgroup -> tile map (longest list first)
+ *   n_emitted  1 uint32: L' <= num_rendered, the (tile, splat) pairs that survived the exact tile culling
+ *   gid, reach, slot (uint32) and depth (float), num_rendered elements each, of which the first L' are written:
+ *     for list position i the Gaussian id, its half-tile reach bits (bit h: rows 8 h .. 8 h + 7 of the tile), its
+ *     emission slot (where the backward writes the pair's gradient record) and the view depth the sort read.
+ *     A position whose slot or id is out of range (buffers that are not this forward's) reads gid = 0xFFFFFFFF.
+ * num_rendered == 0: ranges and order are copied, n_emitted = 0, nothing else is touched (the lists may be NULL).
+ * GS4D_ERR_ARG (gs4d_last_error() begins "debug_tile_lists:") for P <= 0, an empty image, num_rendered < 0 or a
+ * NULL pointer that is needed. */
+int gs4d_debug_tile_lists(int P, int width, int height, int num_rendered, const char *geometry_buffer,
+                          const char *binning_buffer, const char *image_buffer, uint32_t *ranges, uint32_t *order,
+                          uint32_t *n_emitted, uint32_t *gid, uint32_t *reach, uint32_t *slot, float *depth,
+                          void *stream);
+
 /* Diagnostic for the blend backward's pair reduction (no reference counterpart): n pairs of splats, one wave
  * each, reduce given per-lane partial sums to their two 12-float records, once as the blend kernel does (column
  * sums through LDS) and once by permlane swaps (the earlier form, kept for this comparison): the two must agree

@@ -164,6 +164,9 @@ constexpr int kHexLdsWords = 20480;  // 80 KiB: two workgroups per CU, as the re
 // backward's workgroup 0 for the conversion launches), [63] non-finite flag; then kHexHistWords words: per
 // level, the histogram of the points' m_i = max_f |dfeat_{i,l,f}| by binary exponent (bin e counts the m_i
 // in (2^(e-128), 2^(e-127)]: an upper bound of sum_i m_i that integer atomics build the same in every run)
+// a point's anchor cell in LDS: y0 << 16 | x0 as an unsigned word (a plane side is at most 65535, so x0, y0 <=
+// 65534 and no anchor equals the sentinel; a signed word with -1 took every row from 32768 on for "none")
+constexpr uint32_t kHexNoAnchor = 0xFFFFFFFFu;
 constexpr int kHexNanWord = 63, kHexScaleWord = 32, kHexMxWords = 64;
 constexpr int kHexHistBins = 256, kHexHistWords = GS4D_HEXPLANE_MAX_LEVELS * kHexHistBins;
 
@@ -319,7 +322,7 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
     const int npw = hex_points_per_wg(F), cpw = npw / ppc;
     const int fixed = hex_bwd_fixed_words(F), wcap = hex_bwd_window(F);
     float *s_dv = smem;                                            // [6][npw][F]
-    int *s_anc = (int *)(s_dv + 6 * npw * F);                      // [6][npw]: y0 << 16 | x0, -1: none
+    uint32_t *s_anc = (uint32_t *)(s_dv + 6 * npw * F);            // [6][npw]: y0 << 16 | x0, kHexNoAnchor: none
     float2 *s_ixy = (float2 *)(s_anc + 6 * npw);                   // [6][npw]
     int *s_box = (int *)(s_ixy + 6 * npw);                         // [6][4]: ax0, ay0, aw, ah
     int *s_wbox = s_box + 24;                                      // [waves][6][4]
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
             const int n = i < N ? (order ? (int)order[i] : (int)i) : -1;
             if (n < 0) {
                 if (q == 0)
-                    for (int p = 0; p < 6; p++) s_anc[p * npw + j] = -1;
+                    for (int p = 0; p < 6; p++) s_anc[p * npw + j] = kHexNoAnchor;
                 continue;
             }
             const float4 p4 = reinterpret_cast<const float4 *>(pts)[n];
@@ -409,7 +412,7 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
                 *reinterpret_cast<float4 *>(s_dv + (p * npw + j) * F + 4 * q) = make_float4(dv[0], dv[1], dv[2], dv[3]);
                 if (q == 0) {
                     const bool ok = t.x0 >= 0 && t.x0 < pl.W && t.y0 >= 0 && t.y0 < pl.H;  // false for NaN
-                    s_anc[p * npw + j] = ok ? (t.y0 << 16) | t.x0 : -1;
+                    s_anc[p * npw + j] = ok ? ((uint32_t)t.y0 << 16) | (uint32_t)t.x0 : kHexNoAnchor;
                     s_ixy[p * npw + j] = make_float2(t.ix, t.iy);
                 }
                 gpt[kPairC0[p]] += t.gxm * gix;
@@ -432,12 +435,12 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
             int bx[6][4];
 #pragma unroll
             for (int p = 0; p < 6; p++) {
-                const int a = threadIdx.x < npw ? s_anc[p * npw + threadIdx.x] : -1;
-                const bool ok = a >= 0;
-                bx[p][0] = ok ? (a & 0xFFFF) : INT_MAX;
-                bx[p][1] = ok ? (a >> 16) : INT_MAX;
-                bx[p][2] = ok ? (a & 0xFFFF) : INT_MIN;
-                bx[p][3] = ok ? (a >> 16) : INT_MIN;
+                const uint32_t a = threadIdx.x < npw ? s_anc[p * npw + threadIdx.x] : kHexNoAnchor;
+                const bool ok = a != kHexNoAnchor;
+                bx[p][0] = ok ? (int)(a & 0xFFFFu) : INT_MAX;
+                bx[p][1] = ok ? (int)(a >> 16) : INT_MAX;
+                bx[p][2] = ok ? (int)(a & 0xFFFFu) : INT_MIN;
+                bx[p][3] = ok ? (int)(a >> 16) : INT_MIN;
             }
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1)
@@ -477,7 +480,7 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
             if (aw * ah == 0) continue;  // uniform
             const float scale = hex_plane_scale(s_msum[l], mx, l, p);
             const float *dvp = s_dv + p * npw * F;
-            const int *ancp = s_anc + p * npw;
+            const uint32_t *ancp = s_anc + p * npw;
             const float2 *ixyp = s_ixy + p * npw;
             unsigned long long *dpl = dfix + pl.offset;
             // the touched cells: the anchors' box and its +1 neighbours inside the plane
@@ -489,9 +492,9 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
                 // uniform: a box too large even at 4 features per pass -- terms straight to the accumulators
                 for (int e = threadIdx.x; e < npw * F; e += kHexThreads) {
                     const int j = e / F, f = e - j * F;
-                    const int a = ancp[j];
-                    if (a < 0) continue;
-                    const int x0 = a & 0xFFFF, y0 = a >> 16;
+                    const uint32_t a = ancp[j];
+                    if (a == kHexNoAnchor) continue;
+                    const int x0 = (int)(a & 0xFFFFu), y0 = (int)(a >> 16);
                     const float2 ixy = ixyp[j];
                     const float d = dvp[j * F + f];
                     const float xa = (float)(x0 + 1) - ixy.x, xb = ixy.x - (float)x0;
@@ -514,9 +517,9 @@ __global__ __launch_bounds__(kHexThreads) void hexplane_backward_kernel(int N, c
                 // items (point j, tap t, group b): consecutive lanes take a tap's consecutive feature groups
                 for (int e = threadIdx.x; e < npw * 4 * gp; e += kHexThreads) {
                     const int b = e & (gp - 1), t = (e >> lg) & 3, j = e >> (lg + 2);
-                    const int a = ancp[j];
-                    if (a < 0) continue;
-                    const int x0 = a & 0xFFFF, y0 = a >> 16, tx = t & 1, ty = t >> 1;
+                    const uint32_t a = ancp[j];
+                    if (a == kHexNoAnchor) continue;
+                    const int x0 = (int)(a & 0xFFFFu), y0 = (int)(a >> 16), tx = t & 1, ty = t >> 1;
                     if ((tx && x0 + 1 >= pl.W) || (ty && y0 + 1 >= pl.H)) continue;
                     const float2 ixy = ixyp[j];
                     // make_tap's weights: w00 = xa ya, w10 = xb ya, w01 = xa yb, w11 = xb yb
@@ -697,6 +700,7 @@ int gs4d_hexplane_layout_init(gs4d_hexplane_layout *lay, int levels, int F, cons
     int64_t off = 0;
     for (int i = 0; i < 6 * levels; i++) {
         if (W[i] < 1 || H[i] < 1 || W[i] > 65535 || H[i] > 65535) return 1;  // anchors pack as 16 + 16 bits
+        if ((int64_t)W[i] * H[i] > INT_MAX) return 1;                         // cell indices are ints
         lay->plane[i].W = W[i];
         lay->plane[i].H = H[i];
         lay->plane[i].offset = off;
@@ -786,6 +790,17 @@ int gs4d_hexplane_forward(int N, const float *pts, const uint32_t *order, const 
     hipLaunchKernelGGL(hexplane_forward_kernel, dim3((unsigned)((threads + kHexThreads - 1) / kHexThreads)),
                        dim3(kHexThreads), 0, (hipStream_t)stream, N, pts, order, *lay, packed, feat);
     return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+// The backward's plan for F features, from the functions the kernel itself uses: the points one workgroup serves
+// and the 64-bit words of its LDS window (a plane's touched box of nc cells is summed there fp features per pass,
+// fp = F, F/2, ... 4, the first with nc * fp <= window_words; beyond that, by direct atomics).  Host only.
+int gs4d_hexplane_backward_plan(int F, int *points_per_workgroup, int *window_words) {
+    if (F < 4 || F % 4 != 0 || F > 256 || ((F / 4) & (F / 4 - 1)) != 0) return 1;
+    if (!points_per_workgroup || !window_words) return 1;
+    *points_per_workgroup = hex_points_per_wg(F);
+    *window_words = hex_bwd_window(F);
+    return 0;
 }
 
 // backward scratch: the scale words and the 64-bit fixed-point accumulators of the packed buffer

@@ -453,6 +453,13 @@ std::tuple<torch::Tensor, std::vector<torch::Tensor>> hexplane_backward(const to
     return {dpts, grads};
 }
 
+// (points per workgroup, LDS window words) of the backward at F features: a host query, no device needed
+std::tuple<int64_t, int64_t> hexplane_backward_plan(int64_t F) {
+    int npw = 0, window = 0;
+    check(gs4d_hexplane_backward_plan((int)F, &npw, &window), "hexplane backward plan");
+    return {npw, window};
+}
+
 
 // ---- deformation tail + activations (gs4d_deform_tail_forward / _backward)
 static const float *opt_f32(const c10::optional<torch::Tensor> &t, int64_t numel, const char *name) {
@@ -1367,6 +1374,7 @@ PYBIND11_MODULE(_C, m) {
           py::arg("f_dc"), py::arg("f_rest"), py::arg("activate") = true);
     m.def("hexplane_backward", &hexplane_backward, py::arg("pts"), py::arg("planes"), py::arg("packed"),
           py::arg("dfeat"), py::arg("order"), py::arg("deterministic") = true);
+    m.def("hexplane_backward_plan", &hexplane_backward_plan, py::arg("F"));
     m.def("l1_forward", &l1_forward);
     m.def("l1_backward", &l1_backward);
     m.def("l1_loss_grad", &l1_loss_grad);

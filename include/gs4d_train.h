@@ -195,7 +195,8 @@ typedef struct {
     int64_t total; /* floats in the packed buffer */
     gs4d_hexplane_plane plane[6 * GS4D_HEXPLANE_MAX_LEVELS];
 } gs4d_hexplane_layout;
-/* Fills offsets/total from the per-plane sizes W[6*levels], H[6*levels]; param/grad pointers are set by the caller. */
+/* Fills offsets/total from the per-plane sizes W[6*levels], H[6*levels] (each side 1..65535, at most 2^31 - 1 cells
+ * per plane); param/grad pointers are set by the caller. */
 int gs4d_hexplane_layout_init(gs4d_hexplane_layout *lay, int levels, int F, const int *W, const int *H);
 int gs4d_hexplane_pack(const gs4d_hexplane_layout *lay, float *packed, void *stream);
 int gs4d_hexplane_unpack(const gs4d_hexplane_layout *lay, const float *packed, void *stream);
@@ -211,6 +212,12 @@ size_t gs4d_hexplane_backward_scratch_bytes(int N, const gs4d_hexplane_layout *l
 int gs4d_hexplane_backward(int N, const float *pts, const uint32_t *order, const gs4d_hexplane_layout *lay,
                            const float *packed, const float *dfeat, float *dpacked, float *dpts, void *scratch,
                            int deterministic, void *stream);
+/* How the backward serves F features (host only, launches nothing; taken from the functions the kernel uses):
+ * *points_per_workgroup consecutive points of the order share a workgroup, and a plane whose touched box of nc
+ * cells fits *window_words 64-bit words at fp features per pass (fp = F, F/2, ... 4: the first with nc * fp <=
+ * window_words) is summed in an LDS window, a larger one by direct atomics.  Nonzero for an F that
+ * gs4d_hexplane_layout_init refuses. */
+int gs4d_hexplane_backward_plan(int F, int *points_per_workgroup, int *window_words);
 
 /* ---- The field's input points, scene/hexplane.py:20-21 (normalize_aabb with aabb = (max corner, min corner))
  * + :166 (torch.cat((pts, timestamps), -1)) in one pass: pts (N, 4) = ((xyz - aabb[0]) * s - 1, t) with

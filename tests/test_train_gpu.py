@@ -3,7 +3,9 @@ formulations, which are the oracle for these rows (each is a restatement of refe
 cited in gs4d_train/): the fused L1 loss vs utils/loss_utils.l1_loss + autograd, the densification
 statistics vs train.py:346-349 / gaussian_model.py:521-523, FusedAdam vs torch.optim.Adam as the
 reference configures it, the fused HexPlane field vs scene/hexplane.py's F.grid_sample graph, and a
-whole train step fused vs unfused.  Tolerances are stated per test."""
+whole train step fused vs unfused.  Tolerances are stated per test.
+The deformation module's dispatch between these kernels, route by route against the fp64 unfused graph:
+tests/test_deformation_routes_gpu.py (scenes: deformation_route_scenes.py, CPU preconditions: test_deformation_routes_boundary.py)."""
 
 import copy
 import os

@@ -24,13 +24,13 @@ ARCH = os.environ.get("GS4D_ARCH", "gfx950")
 # (the D-SSIM loss), the deformation MLP's mlp_*.hip and deform_infer.hip (the MLP at inference), all compiled alike
 TRAIN_SOURCES = ["train_tail.hip", "ssim.hip", "mlp_feature.hip", "mlp_heads_forward.hip", "mlp_heads_backward.hip", "mlp_gemm.hip",
                  "deform_infer.hip"]
-HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backward.hip", "knn.hip", *TRAIN_SOURCES, "hexplane.hip", "capi.hip", "voxel.hip"]
+HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backward.hip", "camera_grad.hip", "knn.hip", *TRAIN_SOURCES, "hexplane.hip", "capi.hip", "voxel.hip"]
 # Per-Gaussian math (K1, K8/K9) is compiled without FMA contraction: it costs nothing measurable
 # (those kernels are tiny) and keeps radii / tile rects -- discrete decisions -- bit-identical to the
 # oracle.  The per-pixel blend kernels keep contraction for throughput.
 # (package, pybind glue) pairs: each package gets an in-tree `_C` module over libgs4d
 BINDINGS = [("diff_gaussian_rasterization", "torch_glue.cpp"), ("simple_knn", "knn_glue.cpp"), ("gs4d_train", "train_glue.cpp")]
-NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "binning.hip", "knn.hip", "voxel.hip", *TRAIN_SOURCES, "hexplane.hip"}
+NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "camera_grad.hip", "binning.hip", "knn.hip", "voxel.hip", *TRAIN_SOURCES, "hexplane.hip"}
 # The blend kernels pack pixel pairs explicitly (ext_vector_type(2) -> v_pk_*_f32); the SLP vectorizer
 # would also pack their scalar horizontal adds, paying register moves for a v_pk_add_f32 (4 issue cycles)
 # where two v_add_f32 cost about 5 (tools/bench/valu_rates.hip), so it is off for render.hip.

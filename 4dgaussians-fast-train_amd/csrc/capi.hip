@@ -381,7 +381,7 @@ int gs4d_forward_ex(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc
 
 }  // extern "C"
 
-// One backward call, as the seven exported entries hand it to backward_impl: gs4d_backward_absgrad's parameters in
+// One backward call, as the eight exported entries hand it to backward_impl: gs4d_backward_absgrad's parameters in
 // their order, then what the entry requires.
 namespace {
 struct BackwardCall {
@@ -404,6 +404,7 @@ struct BackwardCall {
     int view_transposed;
     bool need_depth, need_abs;  // gs4d_backward_depth / gs4d_backward_absgrad: a NULL dL_ddepth / abs_dmean2D is an error
     const float *aa_opacities = nullptr;  // gs4d_backward_aa with antialiasing: the forward's raw opacities
+    float *dL_dcamera = nullptr;          // gs4d_backward_camera: 35 floats (NULL: no camera gradient)
 };
 }  // namespace
 
@@ -415,7 +416,10 @@ static int backward_impl(const BackwardCall &c) {
     const int debug = c.debug, P = c.P, R = c.R;
     if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "backward: bad sizes");
     if (c.need_abs && !c.abs_dmean2D) return fail(GS4D_ERR_ARG, "backward_absgrad: missing abs_dmean2D");
-    if (P == 0) return GS4D_OK;
+    if (P == 0) {  // no Gaussian, no term: the camera gradient is 35 zeros
+        if (c.dL_dcamera) GS4D_HIP(hipMemsetAsync(c.dL_dcamera, 0, 35 * sizeof(float), stream));
+        return GS4D_OK;
+    }
     if (c.need_depth && (!c.dL_ddepth || !c.dL_dpix))
         return fail(GS4D_ERR_ARG, "backward_depth: missing dL_ddepth or dL_dpix");
     if (!c.geom_buffer || !c.image_buffer || (R > 0 && !c.binning_buffer) || !c.dL_dpix || !c.means3D)
@@ -440,7 +444,7 @@ static int backward_impl(const BackwardCall &c) {
     // segmented-reduction partials
     const size_t rec_bytes = align_up((size_t)R * kContribStride * sizeof(float), 256);
     const size_t dconic_bytes = align_up(16 * (size_t)P, 256);
-    char *scratch = c.scratch_alloc(c.scratch_ctx, rec_bytes + dconic_bytes + contrib_scratch_bytes(R, P) + 256);
+    char *scratch = c.scratch_alloc(c.scratch_ctx, rec_bytes + dconic_bytes + contrib_scratch_bytes(R, P, c.dL_dcamera != nullptr) + 256);
     if (!scratch) return fail(GS4D_ERR_ALLOC, "backward: scratch allocation failed");
     float *contrib = (float *)align_up((size_t)scratch, 256);
     char *reduce_scratch = (char *)contrib + rec_bytes + dconic_bytes;
@@ -461,7 +465,7 @@ static int backward_impl(const BackwardCall &c) {
                launch_gaussian_backward(a, g, R, reduce_scratch, depth, radii_ptr, c.means3D, c.shs, c.scales,
                                         c.rotations, cov3D_ptr, c.dL_dmean2D, dconic, c.dL_dopacity, c.dL_dcolor,
                                         c.dL_dmean3D, c.dL_dcov3D, c.dL_dsh, c.dL_dscale, c.dL_drot, c.abs_dmean2D,
-                                        c.aa_opacities, stream));
+                                        c.aa_opacities, c.dL_dcamera, stream));
     if (c.dL_dconic && (float *)dconic != c.dL_dconic)
         GS4D_HIP(hipMemcpyAsync(c.dL_dconic, dconic, 16 * (size_t)P, hipMemcpyDeviceToDevice, stream));
     end_marks();
@@ -552,6 +556,27 @@ int gs4d_backward_aa(int P, int D, int M, int R, const float *background, int wi
                           dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
                           abs_dmean2D, scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, false,
                           antialiasing ? opacities : nullptr});
+}
+
+int gs4d_backward_camera(int P, int D, int M, int R, const float *background, int width, int height,
+                         const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                         float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                         const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                         float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer,
+                         char *image_buffer, const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha,
+                         float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
+                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D,
+                         gs4d_alloc_fn scratch_alloc, void *scratch_ctx, int debug, void *stream, int view_transposed,
+                         const float *opacities, int antialiasing, float *dL_dcamera) {
+    if (!dL_dcamera) return fail(GS4D_ERR_ARG, "backward_camera: missing dL_dcamera");
+    if (antialiasing && !opacities && P != 0)
+        return fail(GS4D_ERR_ARG, "backward_camera: antialiasing needs the forward's opacities");
+    return backward_impl({P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepth, dL_dalpha, dL_dmean2D,
+                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                          abs_dmean2D, scratch_alloc, scratch_ctx, debug, stream, view_transposed, false, false,
+                          antialiasing ? opacities : nullptr, dL_dcamera});
 }
 
 int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out_alpha, void *stream) {

@@ -223,7 +223,8 @@ hipError_t launch_render_backward(const Args &a, GeomState g, const uint32_t *gi
 hipError_t launch_wave_sum_debug(int n, const float *in, bool depth, bool abs, float *out_lds, float *out_permlane,
                                  hipStream_t s);
 hipError_t render_backward_occupancy(bool depth, bool abs, int *workgroups_per_cu);
-size_t contrib_scratch_bytes(int R, int P);
+// camera: also room for the camera-gradient backward's partial rows (launch_gaussian_backward with dL_dcamera)
+size_t contrib_scratch_bytes(int R, int P, bool camera = false);
 hipError_t launch_contrib_reduce(const Args &a, GeomState g, BinningState b, int R, const float *contrib,
                                  char *scratch, bool depth, float *dL_dmean2D, float4 *dL_dconic,
                                  float *dL_dopacity, float *dL_dcolor, float *abs_dmean2D, hipStream_t s);
@@ -235,7 +236,17 @@ hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scr
                                     const float *rotations, const float *cov3D, float *dL_dmean2D,
                                     float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                                     float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                    float *abs_dmean2D, const float *opacities, hipStream_t s);
+                                    float *abs_dmean2D, const float *opacities, float *dL_dcamera, hipStream_t s);
+// The camera gradient (gs4d_backward_camera): dL_dcamera (35 floats, NULL for none) = dL/dviewmatrix (16, [i][j] at
+// 4 i + j of the matrix as the caller's tensor indexes it), dL/dprojmatrix (16), dL/dcampos (3).  The camera-gradient
+// instantiations of the per-Gaussian kernels leave one row per workgroup -- kCamRow floats, the first 27 used: 12 of
+// dL/dviewmatrix (columns 0..2), 12 of dL/dprojmatrix (columns 0, 1, 3), 3 of dL/dcampos -- in the reduce scratch,
+// and launch_camera_grad_sum (camera_grad.hip) adds the rows in a fixed order and writes all 35 floats.
+constexpr int kCamRow = 32;
+struct CamRows {
+    float *rows;
+};
+hipError_t launch_camera_grad_sum(const float *rows, int n_rows, float *dL_dcamera, hipStream_t s);
 // The two run-time flags as compile-time constants: f(std::bool_constant<depth>{}, std::bool_constant<abs>{}),
 // for the launchers' choice among a kernel's four instantiations.
 template <class F>

@@ -324,10 +324,15 @@ __device__ __forceinline__ void cov2D_to_cov3D(const float (*Tq)[3], float dL_da
 // AA (the antialiased backward): aa_dL_ds = dL/ds = dL/do_eff * o comes in and *aa_s = s goes out; with
 // dL/dr = dL/ds / (2 s), or 0 for a floored s, the terms dL/dr * (dr/da0, dr/db, dr/dc0) join dL_da, dL_db, dL_dc
 // ahead of the chain to dL/dcov3D and dL/dmean -- also where denom2inv == 0 zeroes the conic's own terms.
-template <bool AA = false>
+// CAM (the camera-gradient backward): cam[0..2] = dL/dt, the view-space vector before the view rotation takes it
+// to dL/dmean (clamp zeros included); cam[3..8] = dL/dT, rows 0 and 1 of the gradient of T = J Rv, which the
+// reference needs only through dL/dJ; cam[9..12] = J00, J11, J02, J12.
+constexpr int kCov2DCamValues = 13;
+template <bool AA = false, bool CAM = false>
 __device__ __forceinline__ V3 cov2D_backward(V3 mean, float h_x, float h_y, float tan_fovx, float tan_fovy,
                                              const float cov3D[6], const Mat4 &view, float3 dL_dconic,
-                                             float dL_dcov[6], float aa_dL_ds = 0.f, float *aa_s = nullptr) {
+                                             float dL_dcov[6], float aa_dL_ds = 0.f, float *aa_s = nullptr,
+                                             float *cam = nullptr) {
     V3 t = transformPoint4x3(mean, view);
     const float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
     const float txtz = t.x / t.z, tytz = t.y / t.z;
@@ -394,6 +399,12 @@ __device__ __forceinline__ V3 cov2D_backward(V3 mean, float h_x, float h_y, floa
     float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
     float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 +
                    (2 * h_y * t.y) * tz3 * dL_dJ12;
+    if (CAM) {
+        cam[0] = dL_dtx; cam[1] = dL_dty; cam[2] = dL_dtz;
+        cam[3] = dL_dT00; cam[4] = dL_dT01; cam[5] = dL_dT02;
+        cam[6] = dL_dT10; cam[7] = dL_dT11; cam[8] = dL_dT12;
+        cam[9] = J.m[0][0]; cam[10] = J.m[1][1]; cam[11] = J.m[0][2]; cam[12] = J.m[1][2];
+    }
     return transformVec4x3Transpose(v3(dL_dtx, dL_dty, dL_dtz), view);
 }
 

@@ -181,13 +181,18 @@ __global__ __launch_bounds__(256) void contrib_segments_kernel(const uint32_t *_
 // AA (the antialiased backward; `opacities` = the raw o): the dL_dopacity the reduction left is g = dL/do_eff
 // (conic_opacity.w holds o_eff).  cov2D_backward takes dL/ds = g o into the covariance and returns s, and the
 // stored dL_dopacity becomes dL/do = g s; a Gaussian with radii 0 has no instances and keeps its zero.
-template <int NV, bool ABS, bool AA>
+// CAM (the camera-gradient backward): cam[0..23] receive this Gaussian's terms of dL/dviewmatrix (columns 0..2:
+// cam[3 i + j] = p_h[i] dL/dt[j], plus the rotation's share of T = J Rv in rows 0..2) and of dL/dprojmatrix
+// (columns 0, 1, 3: cam[12 + 3 i + jj] = p_h[i] dL/dp_hom[j]), p_h = (mean, 1); zeros for a Gaussian with radii 0
+// or without instances.  dL/dt carries the clamp's zeros, W3 (NV = 10) and, with AA, the factor's share.
+constexpr int kCamValues = 27;  // 12 + 12 + the 3 of dL/dcampos (the SH kernel's)
+template <int NV, bool ABS, bool AA, bool CAM = false>
 __device__ __forceinline__ V3 gaussian_grads(
     int idx, const Args &a, const GeomState &g, const int *__restrict__ radii, const float *__restrict__ means3D,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ cov3Ds,
     const float *dL_dmean2D, const float4 *dL_dconic, float *__restrict__ dL_dcov3D, float *__restrict__ dL_dscale,
     float *__restrict__ dL_drot, const uint32_t *__restrict__ e_first, const float4 *__restrict__ part,
-    const GradOut &o, const float *__restrict__ opacities) {
+    const GradOut &o, const float *__restrict__ opacities, float *cam = nullptr) {
     {
         const uint32_t ni = g.n_inst[idx];
         if (ni == 0) {
@@ -216,15 +221,16 @@ __device__ __forceinline__ V3 gaussian_grads(
         for (int i = 0; i < 6; i++) cov3D[i] = cov3Ds[6 * (size_t)idx + i];
         const float4 dc = dL_dconic[idx];
         // K8 (backward.cu:144-274): the covariance part of dL/dmean (assigned, :273)
+        float cb[CAM ? kCov2DCamValues : 1];
         if (AA) {
             const float gop = o.opacity[idx];  // pass 1 or this thread wrote it
             float s;
-            dmean = cov2D_backward<true>(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
-                                         make_float3(dc.x, dc.y, dc.w), dcov, gop * opacities[idx], &s);
+            dmean = cov2D_backward<true, CAM>(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
+                                              make_float3(dc.x, dc.y, dc.w), dcov, gop * opacities[idx], &s, cb);
             o.opacity[idx] = gop * s;
         } else {
-            dmean = cov2D_backward(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
-                                   make_float3(dc.x, dc.y, dc.w), dcov);
+            dmean = cov2D_backward<false, CAM>(m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, view,
+                                               make_float3(dc.x, dc.y, dc.w), dcov, 0.f, nullptr, cb);
         }
         // K9 (backward.cu:370-387): projection part
         const float *proj = projm.m;
@@ -241,6 +247,26 @@ __device__ __forceinline__ V3 gaussian_grads(
         if (NV == 10) {  // depth part: W3 times the depth row of the view matrix
             const float w3 = dc.z;
             dmean = dmean + v3(view.m[2] * w3, view.m[6] * w3, view.m[10] * w3);
+        }
+        if (CAM && g.n_inst[idx] != 0) {
+            const float ph[4] = {m.x, m.y, m.z, 1.f};
+            const float dt[3] = {cb[0], cb[1], NV == 10 ? cb[2] + dc.z : cb[2]};
+            // dL/dp_hom of mean2D = p_hom.xy * m_w (column 2, the unused NDC depth, gets nothing)
+            const float dp[3] = {m_w * g2x, m_w * g2y, -(m_hom.x * g2x + m_hom.y * g2y) * m_w * m_w};
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+                    cam[3 * i + j] = ph[i] * dt[j];
+                    cam[12 + 3 * i + j] = ph[i] * dp[j];
+                }
+            // T = J Rv, Rv[b][k] = V[k][b]: dL/dV[k][b] += sum_a dL/dT[a][k] J[a][b]
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                cam[3 * k + 0] += cb[3 + k] * cb[9];
+                cam[3 * k + 1] += cb[6 + k] * cb[10];
+                cam[3 * k + 2] += cb[3 + k] * cb[11] + cb[6 + k] * cb[12];
+            }
         }
         // SH part (backward.cu:390-391): added by the caller
         // cov3D part (backward.cu:394-395)
@@ -265,6 +291,50 @@ __device__ __forceinline__ V3 gaussian_grads(
 // objects, what they were.
 __device__ __forceinline__ const float *raw_opacities() { return nullptr; }
 __device__ __forceinline__ const float *raw_opacities(const float *p) { return p; }
+// The camera-gradient instantiations take, last in the same pack, the partial rows they write: one row of
+// kCamRow floats per workgroup (camera_grad.hip sums them).  The pack is then (CamRows) or (raw opacities, CamRows).
+__device__ __forceinline__ const float *raw_opacities(CamRows) { return nullptr; }
+__device__ __forceinline__ const float *raw_opacities(const float *p, CamRows) { return p; }
+__device__ __forceinline__ float *cam_rows() { return nullptr; }
+__device__ __forceinline__ float *cam_rows(const float *) { return nullptr; }
+__device__ __forceinline__ float *cam_rows(CamRows c) { return c.rows; }
+__device__ __forceinline__ float *cam_rows(const float *, CamRows c) { return c.rows; }
+template <class... Raw>
+constexpr bool kPackAA = (std::is_same<Raw, const float *>::value || ...);
+template <class... Raw>
+constexpr bool kPackCam = (std::is_same<Raw, CamRows>::value || ...);
+
+// The workgroup's sum of each of the kCamValues per-thread values, in a fixed order: inside a wave the scan's DPP
+// moves without the segment flags (row_shr 1, 2, 4, 8, then row_bcast 15 and 31: lane 63 ends with the wave's
+// sum), then the waves' sums in wave order through LDS (consecutive floats: no bank conflict).  Thread q <
+// kCamValues stores value q of the workgroup's row.  Every thread of the workgroup must call it.
+template <int CTRL, int RM>
+__device__ __forceinline__ void cam_sum_step(float (&v)[kCamValues]) {
+#pragma unroll
+    for (int q = 0; q < kCamValues; q++)
+        v[q] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[q]), CTRL, RM, 0xF, false));
+}
+template <int WAVES>
+__device__ __forceinline__ void cam_block_sum(float (&v)[kCamValues], float *__restrict__ row) {
+    __shared__ float sums[WAVES * kCamValues];
+    cam_sum_step<0x111, 0xF>(v);  // row_shr:1
+    cam_sum_step<0x112, 0xF>(v);  // row_shr:2
+    cam_sum_step<0x114, 0xF>(v);  // row_shr:4
+    cam_sum_step<0x118, 0xF>(v);  // row_shr:8
+    cam_sum_step<0x142, 0xA>(v);  // row_bcast:15 -> rows 1, 3
+    cam_sum_step<0x143, 0xC>(v);  // row_bcast:31 -> rows 2, 3
+    if ((threadIdx.x & 63) == 63) {
+#pragma unroll
+        for (int q = 0; q < kCamValues; q++) sums[(threadIdx.x >> 6) * kCamValues + q] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < kCamValues) {
+        float s = sums[threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < WAVES; w++) s += sums[w * kCamValues + threadIdx.x];
+        row[threadIdx.x] = s;
+    }
+}
 
 // Without SH coefficients (colours precomputed): one thread per Gaussian, dL/dmean3D = the two terms.
 template <int NV, bool ABS, class... Raw>
@@ -276,12 +346,25 @@ __global__ __launch_bounds__(256) void gaussian_backward_kernel(
     const uint32_t *__restrict__ e_first, const float4 *__restrict__ part, GradOut o,
     Raw... raw) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= a.P) return;
-    const V3 dmean = gaussian_grads<NV, ABS, sizeof...(Raw) != 0>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
-                                    dL_dcov3D, dL_dscale, dL_drot, e_first, part, o, raw_opacities(raw...));
-    dL_dmean3D[3 * idx + 0] = dmean.x;
-    dL_dmean3D[3 * idx + 1] = dmean.y;
-    dL_dmean3D[3 * idx + 2] = dmean.z;
+    if constexpr (kPackCam<Raw...>) {  // no early exit: the whole workgroup sums (threads past P add zeros)
+        float cam[kCamValues] = {};
+        if (idx < a.P) {
+            const V3 dmean = gaussian_grads<NV, ABS, kPackAA<Raw...>, true>(
+                idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic, dL_dcov3D, dL_dscale,
+                dL_drot, e_first, part, o, raw_opacities(raw...), cam);
+            dL_dmean3D[3 * idx + 0] = dmean.x;
+            dL_dmean3D[3 * idx + 1] = dmean.y;
+            dL_dmean3D[3 * idx + 2] = dmean.z;
+        }
+        cam_block_sum<4>(cam, cam_rows(raw...) + (size_t)blockIdx.x * kCamRow);
+    } else {
+        if (idx >= a.P) return;
+        const V3 dmean = gaussian_grads<NV, ABS, kPackAA<Raw...>>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D, dL_dconic,
+                                        dL_dcov3D, dL_dscale, dL_drot, e_first, part, o, raw_opacities(raw...));
+        dL_dmean3D[3 * idx + 0] = dmean.x;
+        dL_dmean3D[3 * idx + 1] = dmean.y;
+        dL_dmean3D[3 * idx + 2] = dmean.z;
+    }
 }
 
 // With SH coefficients: the same per-Gaussian work and K9's SH part (backward.cu:390-391 -> computeColorFromSH
@@ -326,10 +409,12 @@ __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     }
     V3 dmean = v3(0, 0, 0);
     const int idx = g0 + threadIdx.x;
+    constexpr bool CAM = kPackCam<Raw...>;
+    float cam[CAM ? kCamValues : 1] = {};
     if ((int)threadIdx.x < n)  // pass 2 writes this Gaussian's dL/dcolor (when it spans waves) before it is read
-        dmean = gaussian_grads<NV, ABS, sizeof...(Raw) != 0>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D,
-                                                             dL_dconic, dL_dcov3D, dL_dscale, dL_drot, e_first, part, o,
-                                                             raw_opacities(raw...));
+        dmean = gaussian_grads<NV, ABS, kPackAA<Raw...>, CAM>(idx, a, g, radii, means3D, scales, rotations, cov3Ds, dL_dmean2D,
+                                                              dL_dconic, dL_dcov3D, dL_dscale, dL_drot, e_first, part, o,
+                                                              raw_opacities(raw...), cam);
     __syncthreads();
     if ((int)threadIdx.x < n) {
         float *trow = tile + threadIdx.x * kShRow;
@@ -347,11 +432,17 @@ __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
             const V3 m = v3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
             const V3 dm = sh_backward(a.D, shl, m - load_v3(a.campos), dRGB, trow);
             dmean = dmean + dm;
+            if constexpr (CAM) {  // dir = mean - campos: the centre gets the opposite of the direction's gradient
+                cam[24] = -dm.x;
+                cam[25] = -dm.y;
+                cam[26] = -dm.z;
+            }
         }
         dL_dmean3D[3 * idx + 0] = dmean.x;
         dL_dmean3D[3 * idx + 1] = dmean.y;
         dL_dmean3D[3 * idx + 2] = dmean.z;
     }
+    if constexpr (CAM) cam_block_sum<kShThreads / 64>(cam, cam_rows(raw...) + (size_t)blockIdx.x * kCamRow);
     __syncthreads();
     if (kVec4) {
         float4 *d4 = reinterpret_cast<float4 *>(dL_dsh + base);
@@ -368,9 +459,13 @@ __global__ __launch_bounds__(kShThreads) void gaussian_sh_backward_kernel(
     }
 }
 
-size_t contrib_scratch_bytes(int R, int P) {
+// camera: room for the camera-gradient backward's partial rows, one per workgroup of the per-Gaussian kernel with
+// the smaller workgroup, after e_first
+static size_t cam_rows_max(int P) { return ((size_t)P + kShThreads - 1) / kShThreads; }
+size_t contrib_scratch_bytes(int R, int P, bool camera) {
     const size_t nw = ((size_t)R + 63) / 64;
-    return align_up(nw * 2 * 3 * sizeof(float4), 256) + align_up(4 * (size_t)P, 256) + 256;
+    return align_up(nw * 2 * 3 * sizeof(float4), 256) + align_up(4 * (size_t)P, 256) + 256 +
+           (camera ? align_up(cam_rows_max(P) * kCamRow * sizeof(float), 256) : 0);
 }
 
 static GradOut grad_out(const Args &a, GeomState g, float *dL_dmean2D, float4 *dL_dconic, float *dL_dopacity,
@@ -381,6 +476,9 @@ static float4 *scratch_part(char *scratch) { return (float4 *)scratch; }
 static uint32_t *scratch_e_first(char *scratch, int R) {
     const size_t nw = ((size_t)R + 63) / 64;
     return (uint32_t *)(scratch + align_up(nw * 2 * 3 * sizeof(float4), 256));
+}
+static float *scratch_cam_rows(char *scratch, int R, int P) {
+    return (float *)((char *)scratch_e_first(scratch, R) + align_up(4 * (size_t)P, 256));
 }
 
 template <int NV, bool ABS>
@@ -436,19 +534,24 @@ hipError_t launch_gaussian_backward(const Args &a, GeomState g, int R, char *scr
                                     const float *rotations, const float *cov3D, float *dL_dmean2D,
                                     float4 *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D,
                                     float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot,
-                                    float *abs_dmean2D, const float *opacities, hipStream_t s) {
-    // opacities (the raw ones; NULL for none): the antialiased backward's instantiations
-    return with_backward_variant(depth, abs_dmean2D != nullptr, [&](auto depth_c, auto abs_c) {
+                                    float *abs_dmean2D, const float *opacities, float *dL_dcamera, hipStream_t s) {
+    // opacities (the raw ones; NULL for none): the antialiased backward's instantiations; dL_dcamera (35 floats;
+    // NULL for none): the camera-gradient ones, whose workgroups' rows camera_grad.hip then sums
+    const hipError_t e = with_backward_variant(depth, abs_dmean2D != nullptr, [&](auto depth_c, auto abs_c) {
         constexpr int NV = depth_c.value ? 10 : 9;
         constexpr bool ABS = abs_c.value;
-        if (opacities)
+        const auto run = [&](auto... pack) {
             return gaussian_backward<NV, ABS>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
                                               dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                              dL_drot, abs_dmean2D, s, opacities);
-        return gaussian_backward<NV, ABS>(a, g, R, scratch, radii, means3D, shs, scales, rotations, cov3D, dL_dmean2D,
-                                          dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                          dL_drot, abs_dmean2D, s);
+                                              dL_drot, abs_dmean2D, s, pack...);
+        };
+        const CamRows rows{dL_dcamera ? scratch_cam_rows(scratch, R, a.P) : nullptr};
+        if (opacities) return dL_dcamera ? run(opacities, rows) : run(opacities);
+        return dL_dcamera ? run(rows) : run();
     });
+    if (e != hipSuccess || !dL_dcamera) return e;
+    const int block = shs ? kShThreads : 256;
+    return launch_camera_grad_sum(scratch_cam_rows(scratch, R, a.P), (a.P + block - 1) / block, dL_dcamera, s);
 }
 
 }  // namespace gs4d

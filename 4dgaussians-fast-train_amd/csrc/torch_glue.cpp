@@ -162,7 +162,7 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
                            const int degree, const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
                            const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug,
                            torch::Tensor *abs_out = nullptr, const torch::Tensor *opacities = nullptr,
-             const bool antialiasing = false) {
+             const bool antialiasing = false, torch::Tensor *cam_out = nullptr) {
     if (!means3D.is_cuda()) throw std::runtime_error("means3D must be a HIP (GPU) tensor; the MI355X rasterizer has no CPU path");
     const auto dev = means3D.device();
     c10::hip::HIPGuard guard(dev.index());
@@ -181,6 +181,7 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
     torch::Tensor dL_dscales = torch::empty({P, 3}, opts);
     torch::Tensor dL_drotations = torch::empty({P, 4}, opts);
     if (abs_out) *abs_out = torch::empty({P, 3}, opts);  // gs4d_backward_absgrad writes every row
+    if (cam_out) *cam_out = torch::empty({35}, opts);  // gs4d_backward_camera writes all 35 floats
     if (P != 0) {
         auto bg = prep(background, "bg", dev), m3 = prep(means3D, "means3D", dev), col = prep(colors, "colors_precomp", dev),
              sc = prep(scales, "scales", dev), rot = prep(rotations, "rotations", dev),
@@ -225,7 +226,17 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
         const auto call = [&](const char *what, auto entry, auto images, auto abs_ptr) {
             check_status(std::apply(entry, std::tuple_cat(head, images, outs, abs_ptr, tail)), what);
         };
-        if (opacities) {
+        if (cam_out) {
+            if (!opacities) throw std::runtime_error("the camera-gradient backward takes the forward's opacities");
+            if (antialiasing && opacities->numel() != P) throw std::runtime_error("opacities must have P elements");
+            auto op = prep(*opacities, "opacities", dev);
+            check_status(std::apply(gs4d_backward_camera,
+                                    std::tuple_cat(head, std::make_tuple(pix, dep, alp), outs,
+                                                   std::make_tuple(abs_out ? abs_out->data_ptr<float>() : (float *)nullptr),
+                                                   tail, std::make_tuple(fptr(op), antialiasing ? 1 : 0,
+                                                                         cam_out->data_ptr<float>()))),
+                         "rasterize_gaussians_backward_camera");
+        } else if (opacities) {
             if (antialiasing && opacities->numel() != P) throw std::runtime_error("opacities must have P elements");
             auto op = prep(*opacities, "opacities", dev);
             check_status(std::apply(gs4d_backward_aa,
@@ -242,6 +253,16 @@ BackwardImpl(const torch::Tensor *dL_dout_depth, const torch::Tensor *dL_dout_al
             call("rasterize_gaussians_backward_depth", gs4d_backward_depth, std::make_tuple(pix, dep), std::tuple<>());
         else
             call("rasterize_gaussians_backward", gs4d_backward_ex, std::make_tuple(pix), std::tuple<>());
+    }
+    if (P == 0 && cam_out) {  // no Gaussian: the entry still owes the 35 zeros
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+        check_status(gs4d_backward_camera(0, degree, M, R, nullptr, W, H, nullptr, nullptr, nullptr, nullptr,
+                                          scale_modifier, nullptr, nullptr, nullptr, nullptr, nullptr, tan_fovx, tan_fovy,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, debug ? 1 : 0, (void *)stream, 0, nullptr, antialiasing ? 1 : 0,
+                                          cam_out->data_ptr<float>()),
+                     "rasterize_gaussians_backward_camera");
     }
     return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
                            dL_drotations);
@@ -334,6 +355,31 @@ RasterizeGaussiansBackwardAA(const torch::Tensor &background, const torch::Tenso
                           degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, absgrad ? &abs : nullptr,
                           &opacities, antialiasing);
     return std::tuple_cat(std::move(t), std::make_tuple(abs));
+}
+
+// rasterize_gaussians_backward_aa's arguments; returns its tuple plus dL_dviewmatrix (4, 4), dL_dprojmatrix (4, 4) and
+// dL_dcampos (3), indexed as the matrices the caller passed are (whatever their strides): gs4d_backward_camera
+using CameraTuple = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+                               torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+CameraTuple
+RasterizeGaussiansBackwardCamera(const torch::Tensor &background, const torch::Tensor &means3D,
+                                 const torch::Tensor &radii, const torch::Tensor &colors, const torch::Tensor &scales,
+                                 const torch::Tensor &rotations, const float scale_modifier,
+                                 const torch::Tensor &cov3D_precomp, const torch::Tensor &viewmatrix,
+                                 const torch::Tensor &projmatrix, const float tan_fovx, const float tan_fovy,
+                                 const torch::Tensor &dL_dout_color, const torch::Tensor &dL_dout_depth,
+                                 const torch::Tensor &dL_dout_alpha, const torch::Tensor &sh, const int degree,
+                                 const torch::Tensor &campos, const torch::Tensor &geomBuffer, const int R,
+                                 const torch::Tensor &binningBuffer, const torch::Tensor &imageBuffer, const bool debug,
+                                 const torch::Tensor &opacities, const bool antialiasing, const bool absgrad) {
+    torch::Tensor abs = torch::empty({0}, means3D.options().dtype(torch::kFloat32));
+    torch::Tensor cam;
+    auto t = BackwardImpl(&dL_dout_depth, &dL_dout_alpha, background, means3D, radii, colors, scales, rotations,
+                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                          degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, absgrad ? &abs : nullptr,
+                          &opacities, antialiasing, &cam);
+    return std::tuple_cat(std::move(t), std::make_tuple(abs, cam.slice(0, 0, 16).view({4, 4}),
+                                                        cam.slice(0, 16, 32).view({4, 4}), cam.slice(0, 32, 35)));
 }
 
 // conic_opacity.w of the forward that filled geomBuffer, (P,): gs4d_debug_effective_opacity
@@ -489,6 +535,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians_backward_absgrad", &RasterizeGaussiansBackwardAbsgrad);
     m.def("rasterize_gaussians_aa", &RasterizeGaussiansAA);
     m.def("rasterize_gaussians_backward_aa", &RasterizeGaussiansBackwardAA);
+    m.def("rasterize_gaussians_backward_camera", &RasterizeGaussiansBackwardCamera);
     m.def("debug_effective_opacity", &DebugEffectiveOpacity);
     m.def("debug_tile_lists", &DebugTileLists);
     m.def("alpha_image", &AlphaImage);

@@ -17,7 +17,11 @@ Functions, whose backward also leaves the absolute screen-space gradient (AbsGS;
 `means2D.absgrad`, a (P, 3) tensor overwritten by every backward call.  A fourth, antialiasing=True, is a value
 of the forward and not another Function: the opacity blended is o * sqrt(max(2.5e-5, det S / det(S + 0.3 I))) for
 the projected covariance S (Mip-Splatting's 2-D filter; gsplat's rasterize_mode="antialiased"), and the backward
-carries that factor's gradient into the covariance; radii and the binning do not change.  The compute runs in libgs4d (HIP
+carries that factor's gradient into the covariance; radii and the binning do not change.  A fifth, camera_grad=True,
+makes raster_settings' viewmatrix, projmatrix and campos inputs of the same Function, so the ones that require grad
+receive dL/dviewmatrix, dL/dprojmatrix and dL/dcampos (pose refinement; gsplat's viewmats.grad): the forward is
+unchanged and the backward runs _C.rasterize_gaussians_backward_camera, whose other gradients are bit for bit
+those of the flag-off call.  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
 without the built extension raises ImportError -- there is no CPU fallback.
 """
@@ -68,12 +72,18 @@ def _invoke(fn, args, debug, dump_name, stage):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False):
+                        raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False,
+                        camera_grad=False):
     """(color, radii, depth), or with alpha=True (color, radii, depth, alpha).  absgrad=True: the backward also
     assigns `means2D.absgrad` (P, 3): per Gaussian the sum over its pixels of |the pixel's term of means2D.grad|
     in x and y (column 2 is 0), where means2D.grad holds the signed sum.  antialiasing=True: the footprint-
-    compensated opacity (module docstring) is blended, through the same Function."""
+    compensated opacity (module docstring) is blended, through the same Function.  camera_grad=True:
+    raster_settings.viewmatrix / .projmatrix / .campos follow the switch as inputs and receive their gradients."""
     fn = _FUNCTIONS[bool(depth_grad), bool(alpha), bool(absgrad)]
+    if camera_grad:
+        s = raster_settings
+        return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                        raster_settings, bool(antialiasing), s.viewmatrix, s.projmatrix, s.campos)
     if antialiasing:
         return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, True)
@@ -86,7 +96,8 @@ def _zero_image(channels, s, like):
 
 
 def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-             raster_settings, antialiasing=False):
+             raster_settings, antialiasing=False, *camera):
+    # camera: (viewmatrix, projmatrix, campos), raster_settings' own tensors as inputs of the Function (camera_grad)
     depth_grad, alpha, absgrad = variant
     s = raster_settings
     # positional order of _C.rasterize_gaussians (rasterize_points.h:18-38)
@@ -100,6 +111,8 @@ def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scal
         num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
             _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
     ctx.antialiasing = bool(antialiasing)
+    ctx.aa_input = len(camera) > 0 or bool(antialiasing)  # the switch was an input of the Function
+    ctx.camera_grad = len(camera) > 0
     ctx.variant = variant
     ctx.raster_settings = s
     ctx.num_rendered = num_rendered
@@ -108,7 +121,7 @@ def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scal
     ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf,
-                          binning_buf, img_buf, *((opacities,) if antialiasing else ()))
+                          binning_buf, img_buf, *((opacities,) if antialiasing or camera else ()))
     if absgrad:
         ctx.absgrad_target = means2D  # the caller's tensor: the backward assigns its .absgrad
     if not alpha:
@@ -125,20 +138,21 @@ def _backward(ctx, grad_out_color, grad_depth, grad_alpha):
     s = ctx.raster_settings
     if not depth_grad:  # no gradient flows from the depth image, exactly like the reference (:100-101)
         grad_depth = None
-    extra = (None,) if ctx.antialiasing else ()  # the switch itself, when it was an input
+    # the switch itself, when it was an input, and the three camera tensors after it
+    extra = ((None,) if ctx.aa_input else ()) + ((None,) * 3 if ctx.camera_grad else ())
     if grad_out_color is None and grad_depth is None and grad_alpha is None:
         return (None,) * 9 + extra  # only images without a gradient path were used: nothing flows back
     (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf,
      img_buf) = ctx.saved_tensors[:10]
     # the entry and its upstream images, which follow grad_out_color in its argument list
     tail = ()
-    if ctx.antialiasing:  # one entry for every combination: empty tensors and absgrad=False stand for "off"
-        entry = _C.rasterize_gaussians_backward_aa
+    if ctx.antialiasing or ctx.camera_grad:  # one entry for every combination: empty tensors and False stand for "off"
+        entry = _C.rasterize_gaussians_backward_camera if ctx.camera_grad else _C.rasterize_gaussians_backward_aa
         if grad_out_color is None:
             grad_out_color = _zero_image(3, s, means3D)
         none = torch.empty(0, dtype=torch.float32, device=means3D.device)
         grads = (grad_out_color, none if grad_depth is None else grad_depth, none if grad_alpha is None else grad_alpha)
-        tail = (ctx.saved_tensors[10], True, bool(absgrad))
+        tail = (ctx.saved_tensors[10], ctx.antialiasing, bool(absgrad))
     elif alpha or absgrad:  # an empty tensor stands for "no such gradient"
         entry = _C.rasterize_gaussians_backward_absgrad if absgrad else _C.rasterize_gaussians_backward_aux
         if grad_out_color is None:
@@ -163,6 +177,8 @@ def _backward(ctx, grad_out_color, grad_depth, grad_alpha):
     if absgrad:
         ctx.absgrad_target.absgrad = out[8]  # overwritten per backward call (gsplat's convention)
     g_means2D, g_colors, g_opacities, g_means3D, g_cov3D, g_sh, g_scales, g_rotations = out[:8]
+    if ctx.camera_grad:  # only the camera tensors that require grad take theirs
+        extra = (None,) + tuple(g if need else None for g, need in zip(out[9:12], ctx.needs_input_grad[10:13]))
     return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D, None) + extra
 
 
@@ -232,8 +248,10 @@ def _empty_if_none(t):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False):
+    def __init__(self, raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False,
+                 camera_grad=False):
         super().__init__()
+        self.camera_grad = camera_grad  # opt-in: the settings' camera tensors receive their gradients
         self.antialiasing = antialiasing  # opt-in: the footprint-compensated opacity o * s is blended
         self.absgrad = absgrad  # opt-in: the backward assigns means2D.absgrad (_RasterizeGaussians*Abs)
         self.raster_settings = raster_settings
@@ -257,4 +275,5 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, _empty_if_none(shs), _empty_if_none(colors_precomp), opacities,
                                    _empty_if_none(scales), _empty_if_none(rotations), _empty_if_none(cov3D_precomp),
                                    self.raster_settings, depth_grad=self.depth_grad, alpha=self.alpha,
-                                   absgrad=self.absgrad, antialiasing=self.antialiasing)
+                                   absgrad=self.absgrad, antialiasing=self.antialiasing,
+                                   **({"camera_grad": True} if self.camera_grad else {}))

@@ -50,8 +50,9 @@ class Camera:
     """The fields of scene/cameras.py:Camera that render() reads (cameras.py:17-66)."""
 
     def __init__(self, R, T, FoVx, FoVy, width, height, time=0.0, znear=0.01, zfar=100.0,
-                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0):
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, uid=None):
         self.R, self.T, self.FoVx, self.FoVy = R, T, FoVx, FoVy
+        self.uid = uid  # the camera's row in per-camera tables (gs4d_train.pose.PoseRefiner); None: not in one
         self.image_width, self.image_height = int(width), int(height)
         self.time = time
         self.znear, self.zfar = znear, zfar

@@ -41,7 +41,10 @@ def optimization_params(**over):
              densify_absgrad=False,
              # opt-in (Mip-Splatting's 2-D filter): every view is rendered with antialiasing=True, the
              # footprint-compensated opacity (train.py); render the trained model with the same value
-             antialiasing=False)
+             antialiasing=False,
+             # opt-in (pose refinement): learning rate of the per-camera pose deltas' Adam; read only when
+             # train_step is given a PoseRefiner (train.py), 0 = off
+             pose_lr=0.0)
     d.update(over)
     return SimpleNamespace(**d)
 

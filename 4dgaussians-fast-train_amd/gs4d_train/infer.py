@@ -151,12 +151,15 @@ def get_state_at_time(state, camera):
 
 
 @torch.no_grad()
-def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False):
+def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False, camera_tensors=None):
     """render()'s dict (gaussian_renderer/__init__.py:130-138) for a captured model, through the same rasterizer.
-    antialiasing: render()'s switch; a model trained with it on is rendered with it on."""
+    antialiasing: render()'s switch; a model trained with it on is rendered with it on.  camera_tensors: render()'s
+    (viewmatrix, projmatrix, campos) in place of the camera's own, e.g. a refined pose (PoseRefiner.tensors)."""
     import diff_gaussian_rasterization as dgr
     dev = state.xyz.device
-    if hasattr(camera, "on_device"):
+    if camera_tensors is not None:
+        view_m, proj_m, cam_c = (t.detach() for t in camera_tensors)
+    elif hasattr(camera, "on_device"):
         view_m, proj_m, cam_c = camera.on_device(dev)
     else:
         view_m, proj_m, cam_c = (camera.world_view_transform.to(dev), camera.full_proj_transform.to(dev),

@@ -101,8 +101,12 @@ class RenderPackage(dict):
 
 
 def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False,
-           alpha=False, absgrad=False, antialiasing=False):
-    """antialiasing=True (opt-in): the rasterizer blends the footprint-compensated opacity o * s (Mip-Splatting's 2-D
+           alpha=False, absgrad=False, antialiasing=False, camera_grad=False, camera_tensors=None):
+    """camera_grad=True (opt-in): the backward also differentiates the image with respect to the camera; the view
+    matrix, the full projection and the camera centre that require grad receive their gradients (pose refinement).
+    camera_tensors=(viewmatrix, projmatrix, campos), device tensors, stand in for the camera's own three -- a
+    gs4d_train.pose.PoseRefiner's, typically; they are used with or without camera_grad.
+    antialiasing=True (opt-in): the rasterizer blends the footprint-compensated opacity o * s (Mip-Splatting's 2-D
     filter) and its backward carries s's gradient into the covariance; render a model with the value it was trained
     with.  absgrad=True (opt-in): after the backward, `viewspace_points.absgrad` (P, 3) holds the absolute screen-space
     gradient, the sum over pixels of |each pixel's term of viewspace_points.grad| (AbsGS), overwritten per backward.
@@ -114,7 +118,9 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
     # holds the same values and receives the same .grad)
     screenspace_points = _zero_points(xyz)
     dev = xyz.device
-    if hasattr(viewpoint_camera, "on_device"):
+    if camera_tensors is not None:
+        view_m, proj_m, cam_c = camera_tensors
+    elif hasattr(viewpoint_camera, "on_device"):
         view_m, proj_m, cam_c = viewpoint_camera.on_device(dev)
     else:
         view_m, proj_m, cam_c = (viewpoint_camera.world_view_transform.to(dev),
@@ -128,7 +134,8 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
     # over the P rows (made once per (device, time); no fill per call)
     time = _time_value(_time_float(viewpoint_camera.time), dev).expand(xyz.shape[0], 1)
     rasterizer = dgr.GaussianRasterizer(raster_settings=settings, depth_grad=depth_grad, alpha=alpha,
-                                        absgrad=absgrad, antialiasing=antialiasing)
+                                        absgrad=absgrad, antialiasing=antialiasing,
+                                        **({"camera_grad": True} if camera_grad else {}))
     if "coarse" not in stage and "fine" not in stage:
         raise NotImplementedError(stage)
     if getattr(pc, "fused", False) and getattr(pc, "fused_tail", True) and xyz.is_cuda:

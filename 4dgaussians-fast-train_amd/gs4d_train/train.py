@@ -29,6 +29,11 @@ user's: AbsGS roughly doubles densify_grad_threshold_* (0.0004 for the reference
 Antialiased rasterization (opt-in, Mip-Splatting's 2-D filter): with opt.antialiasing every view is rendered with
 antialiasing=True, the opacity compensated for the rasterizer's 0.3 px^2 low-pass; a model trained so is rendered
 so (infer.render_view / render_set / evaluate take the same switch).
+
+Pose refinement (opt-in): with a gs4d_train.pose.PoseRefiner passed as `pose` and opt.pose_lr > 0, every view is
+rendered through the refiner's camera tensors with camera_grad=True, so the rasterizer's camera gradient reaches the
+per-camera deltas, which an Adam of their own (lr = opt.pose_lr) steps after the Gaussians' optimizer.  The deltas'
+gradients are not reduced across ranks, so a refiner does not combine with data_parallel.
 """
 import functools
 
@@ -48,7 +53,7 @@ def depth_l1(depth, gt_depth):
 
 
 def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine", fused_loss=None,
-               data_parallel=False, render_fn=None):
+               data_parallel=False, render_fn=None, pose=None):
     """views: list of (camera, gt_image (3, H, W)), (camera, gt_image, gt_depth (1, H, W) or (H, W)) or
     (camera, gt_image, gt_depth or None, gt_mask (1, H, W) or (H, W), floats in [0, 1]); the depth is read only
     when opt.lambda_depth != 0 and the mask only when opt.lambda_mask != 0.  Returns the (detached) batch loss
@@ -58,9 +63,22 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     gs4d_train.render.render (the HIP rasterizer).  The multi-process CPU tests pass a torch stand-in.  It is
     called with depth_grad=True and / or alpha=True only for the views that need them, and with absgrad=True for
     every view when opt.densify_absgrad is on (its viewspace_points must then carry .absgrad after the backward),
-    and with antialiasing=True for every view when opt.antialiasing is on."""
+    and with antialiasing=True for every view when opt.antialiasing is on.
+
+    pose: a PoseRefiner; with opt.pose_lr > 0 every view is rendered with camera_grad=True and
+    camera_tensors=pose.tensors(camera), and the refiner's deltas are stepped by their own Adam after the Gaussians'
+    optimizer.  With pose=None or opt.pose_lr == 0 nothing of this runs."""
     if render_fn is None:
         from .render import render as render_fn
+    posing = pose is not None and float(getattr(opt, "pose_lr", 0.0)) > 0.0
+    if posing:
+        if data_parallel:
+            raise ValueError("train_step: pose refinement does not combine with data_parallel=True: the pose "
+                             "gradients are not reduced across ranks (out of scope)")
+        plain_render_fn = render_fn
+
+        def render_fn(cam, *args, **kw):
+            return plain_render_fn(cam, *args, camera_grad=True, camera_tensors=pose.tensors(cam), **kw)
     fused = gaussians.fused if fused_loss is None else fused_loss
     gaussians.update_learning_rate(iteration)
     if iteration % 1000 == 0:
@@ -283,4 +301,18 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
         if iteration < opt.iterations:
             gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
+            if posing:
+                pose_opt = _pose_optimizer(pose, float(opt.pose_lr))
+                pose_opt.step()
+                pose_opt.zero_grad(set_to_none=True)
     return loss_out[0]
+
+
+def _pose_optimizer(pose, lr):
+    """the refiner's own Adam over (rot, trans), made on first use and kept on the refiner"""
+    pose_opt = getattr(pose, "optimizer", None)
+    if pose_opt is None:
+        pose_opt = pose.optimizer = torch.optim.Adam(pose.parameters(), lr=lr)
+    for group in pose_opt.param_groups:
+        group["lr"] = lr
+    return pose_opt

@@ -225,6 +225,34 @@ int gs4d_backward_aa(int P, int D, int M, int R, const float *background, int wi
                      void *scratch_ctx, int debug, void *stream, int view_transposed, const float *opacities,
                      int antialiasing);
 
+/* gs4d_backward_aa plus the gradient with respect to the camera: its arguments, then dL_dcamera, 35 floats on the
+ * device, all of them written: dL/dviewmatrix (16), dL/dprojmatrix (16), dL/dcampos (3), each matrix [i][j] at
+ * 4 i + j of the 4x4 as the caller indexes it (with view_transposed != 0 too: the layout of the gradient does not
+ * follow the input's strides).  The camera enters as t = ([m, 1] V)[:3], p_hom = [m, 1] Pm and dir = m - c, and
+ * Rv = V[:3, :3]^T is the rotation of T = J Rv in cov2D = T Sigma T^t.  With p_h = [m, 1], summed over the
+ * Gaussians with radii > 0 and at least one instance (the others add exact zeros):
+ *     dL/dV[i][j]  += p_h[i] dL/dt[j]        j < 3; dL/dt as computeCov2D's backward forms it (backward.cu:262-264,
+ *                                            the frustum clamp's zeros included), plus W3 on j = 2 with dL_ddepth
+ *     dL/dV[k][b]  += sum_a dL/dT[a][k] J[a][b]    k, b < 3; dL/dT = 2 sym(dL/dcov2D) T Sigma
+ *     dL/dPm[i][j] += p_h[i] dL/dp_hom[j]    dL/dp_hom = (w g.x, w g.y, 0, -(p_hom.x g.x + p_hom.y g.y) w^2),
+ *                                            g = dL_dmean2D, w = 1 / (p_hom.w + 1e-7)
+ *     dL/dc        -= the view-direction part of dL_dmean3D (computeColorFromSH's backward; zero without SHs)
+ * Column 3 of dL/dV and column 2 of dL/dPm are zero.  Radii, rectangles, tile lists and the blend's decisions are
+ * not differentiated, and the clamp holds the clamped t.x / t.y as a constant, as for dL_dmean3D.  The sum runs in
+ * a fixed order without float atomics: per workgroup, then over the workgroups' rows in fp64; two calls give the
+ * same bits.  The other outputs are gs4d_backward_aa's, bit for bit.  P == 0 gives 35 zeros.
+ * Status as gs4d_backward_aa, and GS4D_ERR_ARG for a NULL dL_dcamera. */
+int gs4d_backward_camera(int P, int D, int M, int R, const float *background, int width, int height,
+                         const float *means3D, const float *shs, const float *colors_precomp, const float *scales,
+                         float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                         const float *viewmatrix, const float *projmatrix, const float *campos, float tan_fovx,
+                         float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                         const float *dL_dpix, const float *dL_ddepth, const float *dL_dalpha, float *dL_dmean2D,
+                         float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D,
+                         float *dL_dsh, float *dL_dscale, float *dL_drot, float *abs_dmean2D, gs4d_alloc_fn scratch_alloc,
+                         void *scratch_ctx, int debug, void *stream, int view_transposed, const float *opacities,
+                         int antialiasing, float *dL_dcamera);
+
 /* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.

@@ -30,6 +30,8 @@ HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backwa
 # oracle.  The per-pixel blend kernels keep contraction for throughput.
 # (package, pybind glue) pairs: each package gets an in-tree `_C` module over libgs4d
 BINDINGS = [("diff_gaussian_rasterization", "torch_glue.cpp"), ("simple_knn", "knn_glue.cpp"), ("gs4d_train", "train_glue.cpp")]
+# further sources of a binding's module, compiled with its glue: the opt-in importance binding of the rasterizer's `_C`
+EXTRA_GLUE = {"torch_glue.cpp": ["importance_glue.cpp"]}
 NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "camera_grad.hip", "binning.hip", "knn.hip", "voxel.hip", *TRAIN_SOURCES, "hexplane.hip"}
 # The blend kernels pack pixel pairs explicitly (ext_vector_type(2) -> v_pk_*_f32); the SLP vectorizer
 # would also pack their scalar horizontal adds, paying register moves for a v_pk_add_f32 (4 issue cycles)
@@ -113,9 +115,10 @@ def build(force=False, verbose=False, report=True):
     for pkg, glue_src in BINDINGS:
         mod = module_path(pkg)
         glue = os.path.join(CSRC, glue_src)
+        extra = [os.path.join(CSRC, f) for f in EXTRA_GLUE.get(glue_src, [])]
         rel = os.path.relpath(OUT, os.path.join(HERE, pkg))
-        if force or _newer(mod, [glue, lib, os.path.join(INCLUDE, "gs4d.h"), os.path.join(INCLUDE, "gs4d_train.h")]):
-            cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", glue, "-o", mod,
+        if force or _newer(mod, [glue, *extra, lib, os.path.join(INCLUDE, "gs4d.h"), os.path.join(INCLUDE, "gs4d_train.h")]):
+            cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", glue, *extra, "-o", mod,
                    f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H",
                    "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DHIPBLAS_V2",
                    "-I" + sysconfig.get_paths()["include"]] + ["-I" + p for p in incs] + [

@@ -588,6 +588,37 @@ int gs4d_alpha_image(int width, int height, const char *image_buffer, float *out
     return GS4D_OK;
 }
 
+int gs4d_importance(int P, int width, int height, int num_rendered,
+                    const char *geometry_buffer, const char *binning_buffer, const char *image_buffer,
+                    float *weight_sum, float *weight_max, int32_t *pixel_count,
+                    gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int R = num_rendered;
+    if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "importance: P and num_rendered must be >= 0");
+    if (P == 0) return GS4D_OK;
+    if (width <= 0 || height <= 0) return fail(GS4D_ERR_ARG, "importance: the image must be non-empty");
+    if (!geometry_buffer || (R > 0 && !binning_buffer) || !image_buffer)  // no emission, no binning state
+        return fail(GS4D_ERR_ARG, "importance: missing one of the forward's three buffers");
+    if (!weight_sum || !weight_max || !pixel_count) return fail(GS4D_ERR_ARG, "importance: missing an output");
+    if (!scratch_alloc) return fail(GS4D_ERR_ARG, "importance: missing the scratch allocator");
+    if (R == 0) {  // no emission ran: no Gaussian has a slot
+        GS4D_HIP(hipMemsetAsync(weight_sum, 0, sizeof(float) * (size_t)P, stream));
+        GS4D_HIP(hipMemsetAsync(weight_max, 0, sizeof(float) * (size_t)P, stream));
+        GS4D_HIP(hipMemsetAsync(pixel_count, 0, sizeof(int32_t) * (size_t)P, stream));
+        return GS4D_OK;
+    }
+    Args a = make_args(P, 0, 0, width, height, nullptr, 1.f, nullptr, nullptr, nullptr, 1.f, 1.f, 0);
+    // the three states as backward_impl carves them
+    const int T = a.gx * a.gy;
+    GeomState g = GeomState::carve(const_cast<char *>(geometry_buffer), P, T);
+    ImageState img = ImageState::carve(const_cast<char *>(image_buffer), width, height);
+    BinningState b = BinningState::carve(const_cast<char *>(binning_buffer), R, T);
+    char *scratch = scratch_alloc(scratch_ctx, importance_scratch_bytes(R, P));
+    if (!scratch) return fail(GS4D_ERR_ALLOC, "importance: scratch allocation failed");
+    GS4D_HIP(launch_importance(a, g, b, img, R, scratch, weight_sum, weight_max, pixel_count, stream));
+    return GS4D_OK;
+}
+
 int gs4d_forward(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
                  gs4d_alloc_fn image_alloc, void *image_ctx, int P, int D, int M, const float *background, int width,
                  int height, const float *means3D, const float *shs, const float *colors_precomp,

@@ -256,6 +256,12 @@ hipError_t with_backward_variant(bool depth, bool abs, F &&f) {
 }
 // out_alpha[pix] = 1 - final_T[pix] over the n = W * H pixels of the forward's image state (gs4d_alpha_image)
 hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStream_t s);
+// gs4d_importance (render.hip): the walk over the finished forward's lists leaves one (sum, max, count) record per
+// emission slot in `scratch` (importance_scratch_bytes(R, P)), the segmented reduce and its finishing pass write
+// every row of the three outputs.  R > 0.
+size_t importance_scratch_bytes(int R, int P);
+hipError_t launch_importance(const Args &a, GeomState g, BinningState b, ImageState img, int R, char *scratch,
+                             float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s);
 
 size_t knn_scratch_bytes(int P);
 hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch, hipStream_t s);

@@ -1054,4 +1054,277 @@ hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStr
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// gs4d_importance: the blend weight w = alpha T every (pixel, splat) pair of a finished forward deposited
+// (forward.cu:357-358), reduced per Gaussian to its sum, its maximum and the number of pixels it reached.
+//
+// The walk replays render_forward_kernel's over the lists the forward left sorted (upos holds the sorted
+// emission slots, so nothing is sorted here): the same batches of 64 from the run's start, the same per-batch
+// choice of the falloff<CAP, FOLD> instantiation, the same rule sequence and the same recurrence of T, so every
+// w is the forward's to the bit.  No colour is read.  ONE wave per tile, as the backward has it: a lane holds its
+// column's pixel pair of half tile 0 and of half tile 1, each half skipped for a splat that does not reach it
+// (the forward's wave of that half never saw it) and carrying w = 0 once its pixels are retired (the forward's
+// wave had stopped).  Per splat the lane adds its four pixels as (w00 + w01) + (w10 + w11), the wave reduces the 64
+// lane values with a fixed DPP tree (quad, quad, half row, row, then row_bcast:15 and :31 -- lane 63 ends with
+// ((r3 + r2) + (r0 + r1)) of the row sums), the maximum takes the same tree and the count is four ballot
+// popcounts.  Lane 63 leaves (sum, max, count, 0) in the batch's LDS record array and the batch's lanes store
+// their splats' records at their emission slots: 16 bytes per slot, zeros for a splat not walked (its half bits
+// and the early exit), so every slot below L' is written and nothing is cleared beforehand.
+template <int CTRL, int RM = 0xF>
+__device__ __forceinline__ float dpp_rows(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, RM, 0xF, false));
+}
+// lane 63 of the result holds the wave's total in the fixed order stated above (other lanes: partial values)
+__device__ __forceinline__ float wave_sum_lane63(float v) {
+    v = __fadd_rn(v, dpp_rows<0xB1>(v));        // quad_perm [1, 0, 3, 2]
+    v = __fadd_rn(v, dpp_rows<0x4E>(v));        // quad_perm [2, 3, 0, 1]
+    v = __fadd_rn(v, dpp_rows<0x141>(v));       // row_half_mirror
+    v = __fadd_rn(v, dpp_rows<0x140>(v));       // row_mirror: every lane holds its row's sum
+    v = __fadd_rn(v, dpp_rows<0x142, 0xA>(v));  // row_bcast:15 -> rows 1, 3 (other rows add 0)
+    v = __fadd_rn(v, dpp_rows<0x143, 0xC>(v));  // row_bcast:31 -> rows 2, 3
+    return v;
+}
+// the same tree with max; the values are weights (>= 0), so the 0 a disabled row reads is the identity
+__device__ __forceinline__ float wave_max_lane63(float v) {
+    v = fmaxf(v, dpp_rows<0xB1>(v));
+    v = fmaxf(v, dpp_rows<0x4E>(v));
+    v = fmaxf(v, dpp_rows<0x141>(v));
+    v = fmaxf(v, dpp_rows<0x140>(v));
+    v = fmaxf(v, dpp_rows<0x142, 0xA>(v));
+    v = fmaxf(v, dpp_rows<0x143, 0xC>(v));
+    return v;
+}
+
+__global__ __launch_bounds__(64) void importance_walk_kernel(Args a, const uint2 *__restrict__ ranges,
+                                                             const uint32_t *__restrict__ order,
+                                                             const uint32_t *__restrict__ upos,
+                                                             const uint32_t *__restrict__ gid_by_e,
+                                                             const float4 *__restrict__ splat,
+                                                             float4 *__restrict__ rec) {
+    __shared__ SplatLDS s_sp[64];
+    __shared__ RawLDS s_raw;
+    __shared__ float4 s_rec[64];
+    const int tile = (int)__builtin_amdgcn_readfirstlane(order[blockIdx.x]);
+    const int tx = tile % a.gx, ty = tile / a.gx;
+    const int lane = threadIdx.x;
+    const int px = tx * kBlockX + (lane & 15);
+    const int py0 = ty * kBlockY + (lane >> 4);  // rows py0, py0 + 4 (half 0), py0 + 8, py0 + 12 (half 1)
+    const float pfx = (float)px;
+    const float yc = (float)(ty * kBlockY) + 7.5f;
+    const float ylane = (float)(lane >> 4) - 7.5f;
+    const f2 yl0 = f2{ylane, ylane + 4.f}, yl1 = f2{ylane + 8.f, ylane + 12.f};
+    // the forward's per-lane alpha threshold: 1/255 while the pixel blends, 2 once it is outside or retired
+    const bool xin = px < a.W;
+    f2 thr0 = f2{(xin && py0 < a.H) ? kAlphaMin : 2.f, (xin && py0 + 4 < a.H) ? kAlphaMin : 2.f};
+    f2 thr1 = f2{(xin && py0 + 8 < a.H) ? kAlphaMin : 2.f, (xin && py0 + 12 < a.H) ? kAlphaMin : 2.f};
+    f2 T0 = bc2(1.f), T1 = bc2(1.f);
+    uint2 range = ranges[tile];
+    range.x = __builtin_amdgcn_readfirstlane(range.x);
+    range.y = __builtin_amdgcn_readfirstlane(range.y);
+    // list position first + lane: its emission slot, and that slot's Gaussian id | reach bits.  The slots are
+    // loaded three batches ahead and the ids two, so that no load of an iteration waits for another of the same
+    // iteration; the splat records of the next batch are gathered (LDS-DMA) under the current batch's walk.
+    auto load_slot = [&](uint32_t first) { return first + lane < range.y ? upos[first + lane] : 0u; };
+    auto load_gid = [&](uint32_t first, uint32_t e) { return first + lane < range.y ? gid_by_e[e] : 0u; };
+    uint32_t e0 = 0, e1 = 0, e2 = 0, g0 = 0, g1 = 0;
+    if (range.x < range.y) {
+        e0 = load_slot(range.x);
+        g0 = load_gid(range.x, e0);
+        issue_raw_lds(s_raw, range.x + lane < range.y, g0 & kGidMask, splat);
+        e1 = load_slot(range.x + 64);
+        g1 = load_gid(range.x + 64, e1);
+        e2 = load_slot(range.x + 128);
+    }
+    uint32_t base = range.x;
+    for (; base < range.y; base += 64) {
+        // forward.cu:312-314, both halves (a half that is done alone carries w = 0 from here on)
+        if (ballot(thr0.x < 1.f || thr0.y < 1.f || thr1.x < 1.f || thr1.y < 1.f) == 0) break;
+        SplatRegs nxt;
+        const bool valid = base + lane < range.y;
+        read_raw_lds(nxt, s_raw, lane, valid, yc, false);
+        const uint64_t reach0 = ballot(valid && ((g0 >> kReachShift) & 1u));
+        const uint64_t reach1 = ballot(valid && ((g0 >> (kReachShift + 1)) & 1u));
+        // the forward's per-batch masks, over the whole batch whatever half a splat reaches
+        const uint64_t nonpd = ballot(valid && !conic_pd(nxt.geo, nxt.opc));
+        const bool cap = ballot(valid && nxt.opc.z < kInvCapFree) != 0;
+        __builtin_amdgcn_wave_barrier();
+        s_sp[lane].geo = nxt.geo;
+        s_sp[lane].opc = nxt.opc;
+        s_rec[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+        __builtin_amdgcn_wave_barrier();
+        if (base + 64 < range.y) issue_raw_lds(s_raw, base + 64 + lane < range.y, g1 & kGidMask, splat);
+        const uint32_t g2 = load_gid(base + 128, e2);
+        const uint32_t e3 = load_slot(base + 192);
+        // one half of one splat: the forward's blend() without the colour, returning w
+        auto blend = [&](f2 &T, f2 &thr, const Falloff &f, uint32_t j, auto pwc) {
+            bool k0 = f.alpha.x >= thr.x, k1 = f.alpha.y >= thr.y;  // forward.cu:346-348 (live pixels)
+            if (decltype(pwc)::value && ((nonpd >> j) & 1)) {      // forward.cu:341-342
+                k0 = k0 && f.pw.x <= 0.0f;
+                k1 = k1 && f.pw.y <= 0.0f;
+            }
+            f2 ae = f2{k0 ? f.alpha.x : 0.f, k1 ? f.alpha.y : 0.f};
+            f2 tT = T * (bc2(1.f) - ae);  // forward.cu:349
+            if (ballot(fminf(tT.x, tT.y) < 0.0001f) != 0) {
+                // forward.cu:350-354: not blended, the pixel retires
+                const bool t0 = tT.x < 0.0001f, t1 = tT.y < 0.0001f;
+                ae = f2{t0 ? 0.f : ae.x, t1 ? 0.f : ae.y};
+                tT = f2{t0 ? T.x : tT.x, t1 ? T.y : tT.y};
+                thr = f2{t0 ? 2.f : thr.x, t1 ? 2.f : thr.y};
+            }
+            const f2 w = ae * T;  // forward.cu:357-358
+            T = tT;
+            return w;
+        };
+        auto walk = [&](auto capc, auto pwc) {
+            constexpr bool CAP = decltype(capc)::value, FOLD = !decltype(pwc)::value;
+            for (uint64_t todo = reach0 | reach1; todo != 0; todo &= todo - 1) {
+                const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+                const float4 geo = s_sp[j].geo, opc = s_sp[j].opc;
+                const float dx = geo.x - pfx;
+                const float pa = fmaf(geo.z * dx, dx, opc.y), pb = geo.w * dx;
+                f2 w0 = bc2(0.f), w1 = bc2(0.f);
+                if ((reach0 >> j) & 1) w0 = blend(T0, thr0, falloff<CAP, FOLD>(geo, opc, pa, pb, yl0), j, pwc);
+                if ((reach1 >> j) & 1) w1 = blend(T1, thr1, falloff<CAP, FOLD>(geo, opc, pa, pb, yl1), j, pwc);
+                const float ls = __fadd_rn(__fadd_rn(w0.x, w0.y), __fadd_rn(w1.x, w1.y));
+                const float lm = fmaxf(fmaxf(w0.x, w0.y), fmaxf(w1.x, w1.y));
+                const uint32_t cnt = (uint32_t)(__builtin_popcountll(ballot(w0.x > 0.f)) +
+                                                __builtin_popcountll(ballot(w0.y > 0.f)) +
+                                                __builtin_popcountll(ballot(w1.x > 0.f)) +
+                                                __builtin_popcountll(ballot(w1.y > 0.f)));
+                const float ws = wave_sum_lane63(ls), wm = wave_max_lane63(lm);
+                if (lane == 63) s_rec[j] = make_float4(ws, wm, __uint_as_float(cnt), 0.f);
+            }
+        };
+        if (nonpd != 0) walk(std::true_type{}, std::true_type{});
+        else if (cap) walk(std::true_type{}, std::false_type{});
+        else walk(std::false_type{}, std::false_type{});
+        __builtin_amdgcn_wave_barrier();
+        if (valid) rec[e0] = s_rec[lane];
+        e0 = e1; e1 = e2; e2 = e3;
+        g0 = g1; g1 = g2;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // an early exit may leave the next batch's LDS-DMA loads in flight
+    // the splats behind the exit blended nowhere
+    for (uint32_t i = base + lane; i < range.y; i += 64) rec[upos[i]] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// The per-Gaussian pass, as contrib_segments_kernel (preprocess_backward.hip) has it with (add, max, add) for the
+// operators: one lane per emission slot, a segmented inclusive scan over the wave's 64 slots by DPP moves, a
+// Gaussian's consecutive slots being one segment.  A segment that is a whole Gaussian is written out; a piece
+// continuing from the previous wave goes to part[w][0], one that starts a Gaussian and continues into the next
+// wave to part[w][1]; e_first[g] = the Gaussian's first slot.
+struct ImpAcc {
+    float sum, mx;
+    uint32_t cnt;
+};
+template <int CTRL, int RM>
+__device__ __forceinline__ void imp_scan_step(ImpAcc &v, bool &f) {
+    const bool fu = __builtin_amdgcn_update_dpp(0, (int)f, CTRL, RM, 0xF, false) != 0;
+    const float us = dpp_rows<CTRL, RM>(v.sum), um = dpp_rows<CTRL, RM>(v.mx);
+    const uint32_t uc = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.cnt, CTRL, RM, 0xF, false);
+    if (!f) {
+        v.sum = __fadd_rn(v.sum, us);
+        v.mx = fmaxf(v.mx, um);
+        v.cnt += uc;
+    }
+    f = f || fu;
+}
+__global__ __launch_bounds__(256) void importance_segments_kernel(const uint32_t *__restrict__ n_dev,
+                                                                  const uint32_t *__restrict__ gid_by_e,
+                                                                  const float4 *__restrict__ rec,
+                                                                  float *__restrict__ weight_sum,
+                                                                  float *__restrict__ weight_max,
+                                                                  int32_t *__restrict__ pixel_count,
+                                                                  float4 *__restrict__ part,
+                                                                  uint32_t *__restrict__ e_first) {
+    const int n = (int)__builtin_amdgcn_readfirstlane(*n_dev);
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w * 64 >= n) return;
+    const int e = w * 64 + lane;
+    const bool valid = e < n;
+    const uint32_t key = valid ? gid_by_e[e] & kGidMask : 0xFFFFFFFFu;
+    const float4 r = valid ? rec[e] : make_float4(0.f, 0.f, 0.f, 0.f);
+    ImpAcc v{r.x, r.y, __float_as_uint(r.z)};
+    uint32_t kp = __shfl_up(key, 1), kn = __shfl_down(key, 1);
+    if (lane == 0) kp = e > 0 ? gid_by_e[e - 1] & kGidMask : 0xFFFFFFFFu;
+    if (lane == 63) kn = e + 1 < n ? gid_by_e[e + 1] & kGidMask : 0xFFFFFFFFu;
+    const bool head = valid && key != kp;
+    const bool tail = valid && key != kn;
+    if (head) e_first[key] = (uint32_t)e;
+    bool f = head || lane == 0;
+    imp_scan_step<0x111, 0xF>(v, f);  // row_shr:1
+    imp_scan_step<0x112, 0xF>(v, f);  // row_shr:2
+    imp_scan_step<0x114, 0xF>(v, f);  // row_shr:4
+    imp_scan_step<0x118, 0xF>(v, f);  // row_shr:8
+    imp_scan_step<0x142, 0xA>(v, f);  // row_bcast:15 -> rows 1, 3
+    imp_scan_step<0x143, 0xC>(v, f);  // row_bcast:31 -> rows 2, 3
+    const uint64_t endm = __ballot(valid && (tail || lane == 63));
+    const int fe = __ffsll((unsigned long long)endm) - 1;  // end lane of the first piece
+    const bool head0 = __ballot(head) & 1ull;
+    if (valid && (tail || lane == 63)) {
+        const bool starts = lane != fe || head0;  // the piece starts at its Gaussian's first slot
+        if (starts && tail) {
+            weight_sum[key] = v.sum;
+            weight_max[key] = v.mx;
+            pixel_count[key] = (int32_t)v.cnt;
+        } else {
+            part[(size_t)w * 2 + (starts ? 1 : 0)] = make_float4(v.sum, v.mx, __uint_as_float(v.cnt), 0.f);
+        }
+    }
+}
+// One thread per Gaussian: zeros without slots; the pieces of a Gaussian whose slots span waves in wave order,
+// part[w0][1] then part[w][0] of each following wave up to the one holding its last slot.
+__global__ __launch_bounds__(256) void importance_finish_kernel(int P, const uint32_t *__restrict__ n_inst,
+                                                                const uint32_t *__restrict__ e_first,
+                                                                const float4 *__restrict__ part,
+                                                                float *__restrict__ weight_sum,
+                                                                float *__restrict__ weight_max,
+                                                                int32_t *__restrict__ pixel_count) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= P) return;
+    const uint32_t ni = n_inst[idx];
+    if (ni == 0) {
+        weight_sum[idx] = 0.f;
+        weight_max[idx] = 0.f;
+        pixel_count[idx] = 0;
+        return;
+    }
+    const uint32_t e0 = e_first[idx], w0 = e0 >> 6, w1 = (e0 + ni - 1) >> 6;
+    if (w0 == w1) return;  // the segments kernel wrote it
+    float4 p = part[(size_t)w0 * 2 + 1];
+    float sum = p.x, mx = p.y;
+    uint32_t cnt = __float_as_uint(p.z);
+    for (uint32_t w = w0 + 1; w <= w1; w++) {
+        p = part[(size_t)w * 2];
+        sum = __fadd_rn(sum, p.x);
+        mx = fmaxf(mx, p.y);
+        cnt += __float_as_uint(p.z);
+    }
+    weight_sum[idx] = sum;
+    weight_max[idx] = mx;
+    pixel_count[idx] = (int32_t)cnt;
+}
+
+// scratch: R records | 2 partial records per wave of 64 slots | e_first (P)
+size_t importance_scratch_bytes(int R, int P) {
+    const size_t nw = ((size_t)R + 63) / 64;
+    return align_up((size_t)R * sizeof(float4), 256) + align_up(nw * 2 * sizeof(float4), 256) +
+           align_up(4 * (size_t)P, 256) + 256;
+}
+hipError_t launch_importance(const Args &a, GeomState g, BinningState b, ImageState img, int R, char *scratch,
+                             float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s) {
+    const size_t nw = ((size_t)R + 63) / 64;
+    float4 *rec = (float4 *)align_up((size_t)scratch, 256);
+    float4 *part = (float4 *)((char *)rec + align_up((size_t)R * sizeof(float4), 256));
+    uint32_t *e_first = (uint32_t *)((char *)part + align_up(nw * 2 * sizeof(float4), 256));
+    hipLaunchKernelGGL(importance_walk_kernel, dim3(a.gx * a.gy), dim3(64), 0, s, a, img.ranges, img.order, b.upos,
+                       b.gid_by_e, g.splat, rec);
+    hipLaunchKernelGGL(importance_segments_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, b.scratch,
+                       b.gid_by_e, rec, weight_sum, weight_max, pixel_count, part, e_first);
+    hipLaunchKernelGGL(importance_finish_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a.P, g.n_inst, e_first,
+                       part, weight_sum, weight_max, pixel_count);
+    return hipGetLastError();
+}
+
 }  // namespace gs4d

@@ -524,6 +524,9 @@ static int DebugBackwardOccupancy(bool depth, bool abs) {
     return wgs;
 }
 
+// importance_glue.cpp, compiled into this module: the opt-in blend-weight importance binding
+void bind_importance(pybind11::module_ &m);
+
 PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians", &RasterizeGaussians);
     m.def("debug_pair_alpha", &DebugPairAlpha);
@@ -539,6 +542,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("debug_effective_opacity", &DebugEffectiveOpacity);
     m.def("debug_tile_lists", &DebugTileLists);
     m.def("alpha_image", &AlphaImage);
+    bind_importance(m);  // importance_glue.cpp: gaussian_importance
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });
     m.def("last_timings", &last_timings);

@@ -21,7 +21,9 @@ carries that factor's gradient into the covariance; radii and the binning do not
 makes raster_settings' viewmatrix, projmatrix and campos inputs of the same Function, so the ones that require grad
 receive dL/dviewmatrix, dL/dprojmatrix and dL/dcampos (pose refinement; gsplat's viewmats.grad): the forward is
 unchanged and the backward runs _C.rasterize_gaussians_backward_camera, whose other gradients are bit for bit
-those of the flag-off call.  The compute runs in libgs4d (HIP
+those of the flag-off call.  Beside the Functions, gaussian_importance(...) runs one forward without a graph and
+returns what each Gaussian deposited in it: per Gaussian the sum and the maximum of its blend weights alpha * T and the
+number of pixels it reached (the scores score-based pruning ranks by).  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
 without the built extension raises ImportError -- there is no CPU fallback.
 """
@@ -245,6 +247,40 @@ _FUNCTIONS = {(False, False, False): _RasterizeGaussians, (True, False, False): 
 def _empty_if_none(t):
     # "not provided" travels as an empty tensor (reference :197-207)
     return torch.Tensor([]) if t is None else t
+
+
+@torch.no_grad()
+def gaussian_importance(means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                        cov3D_precomp=None, raster_settings=None, antialiasing=False):
+    """(weight_sum, weight_max, pixel_count, radii) of one view: one forward (antialiased with antialiasing=True)
+    and _C.gaussian_importance over the state it left.  Per Gaussian i, over the pixels the forward blended it
+    into, with w = alpha * T the weight the forward multiplied into the colour: weight_sum[i] = sum w (float32, a
+    fixed summation order), weight_max[i] = max w and pixel_count[i] = the number of those pixels (int32), the
+    last two exact; zeros for a Gaussian the view culls.  No graph is built and nothing here is differentiable."""
+    if raster_settings is None:
+        raise ValueError("gaussian_importance: raster_settings is required")
+    if (shs is None) == (colors_precomp is None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    have_sr = scales is not None or rotations is not None
+    if (cov3D_precomp is None and (scales is None or rotations is None)) or (have_sr and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    s = raster_settings
+    P = means3D.shape[0]
+    if P == 0:
+        f = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        i = torch.empty(0, dtype=torch.int32, device=means3D.device)
+        return f, f.clone(), i, i.clone()
+    args = (s.bg, means3D, _empty_if_none(colors_precomp), opacities, _empty_if_none(scales),
+            _empty_if_none(rotations), s.scale_modifier, _empty_if_none(cov3D_precomp), s.viewmatrix, s.projmatrix,
+            s.tanfovx, s.tanfovy, s.image_height, s.image_width, _empty_if_none(shs), s.sh_degree, s.campos,
+            s.prefiltered, s.debug)
+    if antialiasing:
+        num_rendered, _, _, radii, geom_buf, binning_buf, img_buf = _C.rasterize_gaussians_aa(*args, True)
+    else:
+        num_rendered, _, _, radii, geom_buf, binning_buf, img_buf = _C.rasterize_gaussians(*args)
+    weight_sum, weight_max, pixel_count = _C.gaussian_importance(geom_buf, binning_buf, img_buf, num_rendered, P,
+                                                                 s.image_height, s.image_width)
+    return weight_sum, weight_max, pixel_count, radii
 
 
 class GaussianRasterizer(nn.Module):

@@ -21,6 +21,7 @@ import torch
 from .render import _time_float, _time_value
 
 __all__ = ["prepare", "state_at_time", "get_state_at_time", "render_view", "render_set", "evaluate"]
+# (infer.importance, the opt-in blend-weight scores, is reached by name: the star import stays the playback surface)
 
 # (head, the flag that switches it off, GS4D_ROLE_* of include/gs4d_train.h), in forward_dynamic's order
 _HEADS = (("pos_deform", "no_dx", 0), ("scales_deform", "no_ds", 1), ("rotations_deform", "no_dr", 2),
@@ -150,11 +151,8 @@ def get_state_at_time(state, camera):
     return m3, sc, rot, state.opacity, sh
 
 
-@torch.no_grad()
-def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False, camera_tensors=None):
-    """render()'s dict (gaussian_renderer/__init__.py:130-138) for a captured model, through the same rasterizer.
-    antialiasing: render()'s switch; a model trained with it on is rendered with it on.  camera_tensors: render()'s
-    (viewmatrix, projmatrix, campos) in place of the camera's own, e.g. a refined pose (PoseRefiner.tensors)."""
+def _raster_settings(camera, state, bg, scaling_modifier=1.0, camera_tensors=None):
+    """render()'s GaussianRasterizationSettings for `camera` (gaussian_renderer/__init__.py:37-55)."""
     import diff_gaussian_rasterization as dgr
     dev = state.xyz.device
     if camera_tensors is not None:
@@ -164,17 +162,53 @@ def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False, cam
     else:
         view_m, proj_m, cam_c = (camera.world_view_transform.to(dev), camera.full_proj_transform.to(dev),
                                  camera.camera_center.to(dev))
-    settings = dgr.GaussianRasterizationSettings(
+    return dgr.GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
         tanfovx=math.tan(camera.FoVx * 0.5), tanfovy=math.tan(camera.FoVy * 0.5), bg=bg,
         scale_modifier=scaling_modifier, viewmatrix=view_m, projmatrix=proj_m, sh_degree=state.active_sh_degree,
         campos=cam_c, prefiltered=False, debug=False)
+
+
+@torch.no_grad()
+def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False, camera_tensors=None):
+    """render()'s dict (gaussian_renderer/__init__.py:130-138) for a captured model, through the same rasterizer.
+    antialiasing: render()'s switch; a model trained with it on is rendered with it on.  camera_tensors: render()'s
+    (viewmatrix, projmatrix, campos) in place of the camera's own, e.g. a refined pose (PoseRefiner.tensors)."""
+    import diff_gaussian_rasterization as dgr
+    settings = _raster_settings(camera, state, bg, scaling_modifier, camera_tensors)
     m3, sc, rot, op, sh = state_at_time(state, camera.time, activate=True)
     image, radii, depth = dgr.GaussianRasterizer(raster_settings=settings, antialiasing=antialiasing)(
         means3D=m3, means2D=state.zero_points, shs=sh, colors_precomp=None, opacities=op, scales=sc, rotations=rot,
         cov3D_precomp=None)
     return {"render": image, "viewspace_points": state.zero_points, "visibility_filter": radii > 0, "radii": radii,
             "depth": depth}
+
+
+@torch.no_grad()
+def importance(state, cameras, antialiasing=False):
+    """Blend-weight importance of every Gaussian over `cameras` ((camera, time) views): {"sum", "max", "count",
+    "views"}, four (P,) tensors.  For each camera, in order: the state at its time, one forward, and the pass that
+    keeps what the forward's blend deposited (diff_gaussian_rasterization.gaussian_importance).  With w = alpha * T
+    of a (pixel, Gaussian) pair: "sum" (float64) adds each view's per-Gaussian sum of w, view by view in list order
+    (LightGaussian's / Mini-Splatting's importance); "max" (float32) is the largest w over all rays (RadSplat's
+    score); "count" (int64) the number of pixels reached (LightGaussian's hit count); "views" (int64) the number
+    of views with radii > 0.  The same camera list gives the same bits."""
+    import diff_gaussian_rasterization as dgr
+    dev = state.xyz.device
+    P = state.xyz.shape[0]
+    out = {"sum": torch.zeros(P, dtype=torch.float64, device=dev), "max": torch.zeros(P, dtype=torch.float32, device=dev),
+           "count": torch.zeros(P, dtype=torch.int64, device=dev), "views": torch.zeros(P, dtype=torch.int64, device=dev)}
+    bg = torch.zeros(3, dtype=torch.float32, device=dev)  # the weights do not depend on it
+    for cam in cameras:
+        settings = _raster_settings(cam, state, bg)
+        m3, sc, rot, op, sh = state_at_time(state, cam.time, activate=True)
+        wsum, wmax, count, radii = dgr.gaussian_importance(m3, op, shs=sh, scales=sc, rotations=rot,
+                                                           raster_settings=settings, antialiasing=antialiasing)
+        out["sum"] += wsum.double()
+        out["max"] = torch.maximum(out["max"], wmax)
+        out["count"] += count.long()
+        out["views"] += (radii > 0).long()
+    return out
 
 
 def _sync(state):

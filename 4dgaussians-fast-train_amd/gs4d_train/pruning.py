@@ -8,11 +8,20 @@ the reference's.  Normals are not carried: `create_from_pcd` never reads them.
 
 `GaussianModel`, `create_from_pcd`, `render()` and `train_step()` do not know about this module; a caller opts in
 through `initialize(..., use_grid_pruning=True)`.
+
+The other end of training is here too (no reference counterpart): `prune_by_importance` removes the Gaussians of a
+trained or training model that deposit little in any of a set of (camera, time) views, by the blend-weight scores
+of `infer.importance` -- RadSplat's rule on the largest weight, LightGaussian's / Mini-Splatting's ranking by the
+summed weight or the hit count.  The training loop calls it where it wants; `train_step()` does not.
 """
+import math
+
 import numpy as np
 import torch
 
 __all__ = ["voxel_downsample", "adaptive_voxel_size", "grid_pruning", "grid_pruning_with_motion", "initialize"]
+# (importance_mask and prune_by_importance, the score-based pruning, are reached by name: the star import stays the
+# grid pruning's surface)
 
 
 def _device_f32(x, device="cuda"):
@@ -133,3 +142,44 @@ def initialize(gaussians, points, colors, spatial_lr_scale, cameras=None, use_gr
         # create_from_pcd takes host arrays (it is not touched): the pruned cloud makes one round trip
         points, colors = p.cpu().numpy(), c.cpu().numpy()
     gaussians.create_from_pcd(points, colors, spatial_lr_scale)
+
+
+def importance_mask(scores, min_max_weight=None, keep_fraction=None, by="sum"):
+    """The boolean prune mask (True = remove) from `infer.importance`'s scores.  A row is pruned if
+    scores["max"] < min_max_weight (RadSplat's rule), and also if it falls outside the top ceil(keep_fraction * P)
+    rows by scores[by] ("sum", "max", "count" or "views"), ties going to the lower index; both conditions are OR-ed.
+    ValueError when neither is given, for keep_fraction outside (0, 1] and for an unknown `by`."""
+    if min_max_weight is None and keep_fraction is None:
+        raise ValueError("importance_mask: give min_max_weight, keep_fraction or both")
+    if by not in ("sum", "max", "count", "views") or by not in scores:
+        raise ValueError(f"importance_mask: unknown score {by!r}")
+    if keep_fraction is not None and not (0.0 < keep_fraction <= 1.0):
+        raise ValueError("importance_mask: keep_fraction must lie in (0, 1]")
+    P = scores["max"].shape[0]
+    prune = torch.zeros(P, dtype=torch.bool, device=scores["max"].device)
+    if min_max_weight is not None:
+        prune |= scores["max"] < min_max_weight
+    if keep_fraction is not None:
+        keep = min(P, math.ceil(keep_fraction * P))
+        order = torch.sort(scores[by], descending=True, stable=True).indices  # equal scores: the lower index first
+        outside = torch.ones(P, dtype=torch.bool, device=prune.device)
+        outside[order[:keep]] = False
+        prune |= outside
+    return prune
+
+
+def prune_by_importance(gaussians, cameras, min_max_weight=None, keep_fraction=None, by="sum", antialiasing=False):
+    """Score `gaussians` over `cameras` and remove the rows importance_mask selects: infer.prepare, infer.importance,
+    importance_mask, then gaussians.prune_points(mask), i.e. the fused row surgery, so the optimizer state and the
+    densification statistics stay consistent.  Returns (n_removed, scores), the scores being those of the model
+    before the removal.  Call it where the schedule wants it (after the last densification, before an export);
+    an InferenceState prepared earlier is stale afterwards."""
+    from . import infer
+    importance_mask({"max": torch.zeros(0), by: torch.zeros(0)}, min_max_weight, keep_fraction, by)  # argument errors first
+    state = infer.prepare(gaussians)
+    scores = infer.importance(state, cameras, antialiasing=antialiasing)
+    mask = importance_mask(scores, min_max_weight, keep_fraction, by)
+    n_removed = int(mask.sum())
+    if n_removed:
+        gaussians.prune_points(mask)
+    return n_removed, scores

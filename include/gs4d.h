@@ -253,6 +253,33 @@ int gs4d_backward_camera(int P, int D, int M, int R, const float *background, in
                          void *scratch_ctx, int debug, void *stream, int view_transposed, const float *opacities,
                          int antialiasing, float *dL_dcamera);
 
+/* Per-Gaussian blend-weight importance of a finished forward (no reference counterpart; opt-in).  The reference
+ * forms the blend weight of every (pixel, splat) pair, alpha * T, only to multiply it into the colour
+ * (forward.cu:357-358), and returns no such quantity: its rasterizer hands out colour, radii and depth only.
+ * This entry reads the state a finished gs4d_forward / _ex / _aa over P Gaussians left in its three buffers, carved
+ * exactly as gs4d_backward carves them, and replays the blend walk.  For Gaussian i, over the pixels p where the
+ * forward blended it, w_ip = alpha_ip T_ip under the forward's own rules (pixels inside the image, alpha >= 1/255,
+ * power <= 0 for a conic that is not positive definite, the 0.99 cap, and the splat that would drop T below 1e-4
+ * not blended with the pixel retired, forward.cu:330-366); after gs4d_forward_aa the geometry state holds the
+ * compensated opacity, so the weights are the antialiased forward's.
+ *   weight_sum[i]  = sum_p w_ip    (LightGaussian's / Mini-Splatting's importance)
+ *   weight_max[i]  = max_p w_ip    (RadSplat's pruning score)
+ *   pixel_count[i] = #{p : i blends into p}    (LightGaussian's hit count)
+ * Every row of the three outputs (P each, device) is written; a Gaussian with radii == 0, or with no instance that
+ * survived the exact culling, gets exact zeros, and num_rendered == 0 writes P rows of zeros.  Every w_ip is bit
+ * for bit the value the forward multiplied into the colour, so weight_max and pixel_count are exact statements
+ * about the forward that ran.  weight_sum is summed in a fixed order -- within a wave, then per emission slot,
+ * then over a Gaussian's consecutive slots -- without float atomics: two calls give the same bits.  Nothing
+ * synchronises; all launches go to `stream`; the forward's buffers and outputs are left as they are.  The scratch
+ * (per-slot records) comes from scratch_alloc and must stay valid until the stream has run the launches.
+ * Status: GS4D_OK at once for P == 0; GS4D_ERR_ARG (message beginning "importance:") for P < 0, an empty image,
+ * num_rendered < 0, or with P > 0 a NULL buffer (binning_buffer may be NULL when num_rendered == 0), output or
+ * allocator; GS4D_ERR_ALLOC when scratch_alloc returns NULL. */
+int gs4d_importance(int P, int width, int height, int num_rendered,
+                    const char *geometry_buffer, const char *binning_buffer, const char *image_buffer,
+                    float *weight_sum, float *weight_max, int32_t *pixel_count,
+                    gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream);
+
 /* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.

@@ -30,8 +30,9 @@ HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backwa
 # oracle.  The per-pixel blend kernels keep contraction for throughput.
 # (package, pybind glue) pairs: each package gets an in-tree `_C` module over libgs4d
 BINDINGS = [("diff_gaussian_rasterization", "torch_glue.cpp"), ("simple_knn", "knn_glue.cpp"), ("gs4d_train", "train_glue.cpp")]
-# further sources of a binding's module, compiled with its glue: the opt-in importance binding of the rasterizer's `_C`
-EXTRA_GLUE = {"torch_glue.cpp": ["importance_glue.cpp"]}
+# further sources of a binding's module, compiled with its glue: the opt-in importance and feature-rendering bindings
+# of the rasterizer's `_C`
+EXTRA_GLUE = {"torch_glue.cpp": ["importance_glue.cpp", "features_glue.cpp"]}
 NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "camera_grad.hip", "binning.hip", "knn.hip", "voxel.hip", *TRAIN_SOURCES, "hexplane.hip"}
 # The blend kernels pack pixel pairs explicitly (ext_vector_type(2) -> v_pk_*_f32); the SLP vectorizer
 # would also pack their scalar horizontal adds, paying register moves for a v_pk_add_f32 (4 issue cycles)

@@ -619,6 +619,103 @@ int gs4d_importance(int P, int width, int height, int num_rendered,
     return GS4D_OK;
 }
 
+int gs4d_feature_chunk(void) { return feature_chunk(); }
+
+int gs4d_features_forward(int P, int C, int width, int height, int num_rendered, const char *geometry_buffer,
+                          const char *binning_buffer, const char *image_buffer, const float *features,
+                          float *out_image, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream_) {
+    (void)scratch_alloc;  // the pass reads the rows in place and takes no scratch
+    (void)scratch_ctx;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int R = num_rendered;
+    if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "features: P and num_rendered must be >= 0");
+    if (C < 1) return fail(GS4D_ERR_ARG, "features: C must be >= 1");
+    if (P == 0) return GS4D_OK;
+    if (width <= 0 || height <= 0) return fail(GS4D_ERR_ARG, "features: the image must be non-empty");
+    if (!geometry_buffer || (R > 0 && !binning_buffer) || !image_buffer)
+        return fail(GS4D_ERR_ARG, "features: missing one of the forward's three buffers");
+    if (!features || !out_image) return fail(GS4D_ERR_ARG, "features: missing the features or the output image");
+    if (R == 0) {  // no emission ran: nothing was blended anywhere
+        GS4D_HIP(hipMemsetAsync(out_image, 0, sizeof(float) * (size_t)C * width * height, stream));
+        return GS4D_OK;
+    }
+    Args a = make_args(P, 0, 0, width, height, nullptr, 1.f, nullptr, nullptr, nullptr, 1.f, 1.f, 0);
+    const int T = a.gx * a.gy;
+    GeomState g = GeomState::carve(const_cast<char *>(geometry_buffer), P, T);
+    ImageState img = ImageState::carve(const_cast<char *>(image_buffer), width, height);
+    BinningState b = BinningState::carve(const_cast<char *>(binning_buffer), R, T);
+    GS4D_HIP(launch_features_forward(a, C, g, b, img, features, out_image, stream));
+    return GS4D_OK;
+}
+
+int gs4d_features_backward(int P, int C, int R, int width, int height, const float *means3D, const float *scales,
+                           float scale_modifier, const float *rotations, const float *cov3D_precomp,
+                           const float *viewmatrix, const float *projmatrix, float tan_fovx, float tan_fovy,
+                           const int *radii, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                           const float *features, const float *dL_dfeature_image, float *dL_dfeatures,
+                           float *dL_dmean2D, float *dL_dopacity, float *dL_dmean3D, float *dL_dcov3D,
+                           float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
+                           void *stream_, int view_transposed, const float *opacities, int antialiasing) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0 || R < 0) return fail(GS4D_ERR_ARG, "features: P and num_rendered must be >= 0");
+    if (C < 1) return fail(GS4D_ERR_ARG, "features: C must be >= 1");
+    if (P == 0) return GS4D_OK;
+    if (width <= 0 || height <= 0) return fail(GS4D_ERR_ARG, "features: the image must be non-empty");
+    if (!geom_buffer || (R > 0 && !binning_buffer) || !image_buffer)
+        return fail(GS4D_ERR_ARG, "features: missing one of the forward's three buffers");
+    if (!features || !dL_dfeature_image || !dL_dfeatures)
+        return fail(GS4D_ERR_ARG, "features: missing the features, the upstream image or dL_dfeatures");
+    const bool geom = dL_dmean2D != nullptr;  // NULL: the geometry gradients are not wanted (and none is written)
+    if (geom) {
+        if (!dL_dopacity || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot)
+            return fail(GS4D_ERR_ARG, "features: missing a geometry gradient output");
+        if (!means3D || !viewmatrix || !projmatrix) return fail(GS4D_ERR_ARG, "features: missing camera or means3D");
+        if ((!scales || !rotations) && !cov3D_precomp)
+            return fail(GS4D_ERR_ARG, "features: missing scales and rotations, or cov3D_precomp");
+        if (((size_t)rotations & 15) != 0 || ((size_t)dL_drot & 15) != 0)
+            return fail(GS4D_ERR_ARG, "features: rotations and dL_drot must be 16-byte aligned");
+        if (antialiasing && !opacities) return fail(GS4D_ERR_ARG, "features: antialiasing needs the forward's opacities");
+    }
+    if (!scratch_alloc) return fail(GS4D_ERR_ARG, "features: missing the scratch allocator");
+    Args a = make_args(P, 0, 0, width, height, nullptr, scale_modifier, viewmatrix, projmatrix, nullptr, tan_fovx,
+                       tan_fovy, 0);
+    a.view_transposed = view_transposed ? 1 : 0;
+    const int T = a.gx * a.gy;
+    GeomState g = GeomState::carve(geom_buffer, P, T);
+    ImageState img = ImageState::carve(image_buffer, width, height);
+    // scratch: dL/df records, their partials and e_first | geometry records | per-Gaussian conic and (zero) colour gradients | reduce scratch
+    const size_t frec_bytes = features_scratch_bytes(R, P);
+    const size_t rec_bytes = geom ? align_up((size_t)R * kContribStride * sizeof(float), 256) : 0;
+    const size_t dconic_bytes = geom ? align_up(16 * (size_t)P, 256) : 0;
+    const size_t dcolor_bytes = geom ? align_up(12 * (size_t)P, 256) : 0;
+    char *scratch = scratch_alloc(scratch_ctx, frec_bytes + rec_bytes + dconic_bytes + dcolor_bytes +
+                                                   (geom ? contrib_scratch_bytes(R, P) : 0) + 256);
+    if (!scratch) return fail(GS4D_ERR_ALLOC, "features: scratch allocation failed");
+    if (R == 0)  // no emission ran: no Gaussian has a slot (otherwise the per-Gaussian reduce writes every row)
+        GS4D_HIP(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)P * C, stream));
+    char *frec = (char *)align_up((size_t)scratch, 256);
+    float *contrib = geom ? (float *)(frec + frec_bytes) : nullptr;
+    BinningState b = {};
+    if (R > 0) {
+        b = BinningState::carve(binning_buffer, R, T);
+        GS4D_HIP(launch_features_backward(a, C, R, g, b, img, features, dL_dfeature_image, contrib, frec, dL_dfeatures,
+                                          stream));
+    }
+    if (!geom) return GS4D_OK;
+    float4 *dconic = (float4 *)((char *)contrib + rec_bytes);
+    float *dcolor = (float *)((char *)dconic + dconic_bytes);
+    char *reduce_scratch = (char *)dcolor + dcolor_bytes;
+    const float *cov3D_ptr = cov3D_precomp ? cov3D_precomp : g.cov3D;
+    // the existing per-Gaussian stages, fed by this second source of 2-D gradients: no depth, no absgrad, no SH
+    GS4D_HIP(launch_contrib_reduce(a, g, b, R, contrib, reduce_scratch, false, dL_dmean2D, dconic, dL_dopacity, dcolor,
+                                   nullptr, stream));
+    GS4D_HIP(launch_gaussian_backward(a, g, R, reduce_scratch, false, radii ? radii : g.radii, means3D, nullptr, scales,
+                                      rotations, cov3D_ptr, dL_dmean2D, dconic, dL_dopacity, dcolor, dL_dmean3D,
+                                      dL_dcov3D, nullptr, dL_dscale, dL_drot, nullptr,
+                                      antialiasing ? opacities : nullptr, nullptr, stream));
+    return GS4D_OK;
+}
+
 int gs4d_forward(gs4d_alloc_fn geometry_alloc, void *geometry_ctx, gs4d_alloc_fn binning_alloc, void *binning_ctx,
                  gs4d_alloc_fn image_alloc, void *image_ctx, int P, int D, int M, const float *background, int width,
                  int height, const float *means3D, const float *shs, const float *colors_precomp,

@@ -262,6 +262,19 @@ hipError_t launch_alpha_image(ImageState img, size_t n, float *out_alpha, hipStr
 size_t importance_scratch_bytes(int R, int P);
 hipError_t launch_importance(const Args &a, GeomState g, BinningState b, ImageState img, int R, char *scratch,
                              float *weight_sum, float *weight_max, int32_t *pixel_count, hipStream_t s);
+// gs4d_features_forward / gs4d_features_backward (render.hip): the caller's feature rows (P x C) blended with the
+// finished forward's weights, feature_chunk() channels per walk, and the backward of that image.  The backward
+// leaves per-instance geometry records in `contrib` (the kContribStride layout with zero colour and depth fields,
+// for launch_contrib_reduce; NULL: no geometry gradient wanted) and writes every element of dL_df (P x C) through the
+// per-instance records, the segmented reduce's partials and e_first in `fscratch` (features_scratch_bytes(R, P), 256-
+// byte aligned).  R > 0.
+int feature_chunk();
+size_t features_scratch_bytes(int R, int P);
+hipError_t launch_features_forward(const Args &a, int C, GeomState g, BinningState b, ImageState img,
+                                   const float *features, float *out_image, hipStream_t s);
+hipError_t launch_features_backward(const Args &a, int C, int R, GeomState g, BinningState b, ImageState img,
+                                    const float *features, const float *dL_dF, float *contrib, char *fscratch,
+                                    float *dL_df, hipStream_t s);
 
 size_t knn_scratch_bytes(int P);
 hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch, hipStream_t s);

@@ -1327,4 +1327,492 @@ hipError_t launch_importance(const Args &a, GeomState g, BinningState b, ImageSt
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// gs4d_features_forward / gs4d_features_backward: a caller's per-Gaussian feature rows f (P x C) blended with the
+// weights w = alpha T of a finished forward, F_c(p) = sum_i w_ip f_ic, and that image's gradient.
+//
+// Forward: importance_walk_kernel's replay (same batches, falloff<CAP, FOLD> choice, rule sequence and recurrence
+// of T, so every w is the forward's to the bit) with kFeatureChunk accumulators per pixel, each updated as the
+// forward updates a colour channel, acc = fma(f, w, acc) in list order: a channel is bit for bit what the forward
+// blends for that colour over a zero background.  Chunks of kFeatureChunk channels are the grid's y dimension;
+// the rows are read in place (channels past C read as 0 and are not stored), so the pass takes no scratch.  A
+// batch's feature rows sit in LDS beside its splat records (lane l stages its splat's chunk, loaded one batch
+// ahead); the walk reads them wave-uniformly.
+constexpr int kFeatureChunk = 8;
+struct FeatRow {
+    float4 lo, hi;  // channels 0..3 and 4..7 of the chunk
+};
+static_assert(kFeatureChunk == 8, "FeatRow holds two float4");
+__device__ __forceinline__ void load_feat_row(float (&f)[kFeatureChunk], bool valid, uint32_t gid, int C, int c0,
+                                              const float *__restrict__ features) {
+#pragma unroll
+    for (int k = 0; k < kFeatureChunk; k++)
+        f[k] = (valid && c0 + k < C) ? features[(size_t)gid * C + c0 + k] : 0.f;
+}
+
+__global__ __launch_bounds__(64) void feature_walk_kernel(Args a, int C, const uint2 *__restrict__ ranges,
+                                                          const uint32_t *__restrict__ order,
+                                                          const uint32_t *__restrict__ upos,
+                                                          const uint32_t *__restrict__ gid_by_e,
+                                                          const float4 *__restrict__ splat,
+                                                          const float *__restrict__ features,
+                                                          float *__restrict__ out) {
+    constexpr int K = kFeatureChunk;
+    __shared__ SplatLDS s_sp[64];
+    __shared__ RawLDS s_raw;
+    __shared__ FeatRow s_feat[64];
+    const int c0 = (int)blockIdx.y * K;
+    const int tile = (int)__builtin_amdgcn_readfirstlane(order[blockIdx.x]);
+    const int tx = tile % a.gx, ty = tile / a.gx;
+    const int lane = threadIdx.x;
+    const int px = tx * kBlockX + (lane & 15);
+    const int py0 = ty * kBlockY + (lane >> 4);  // rows py0, py0 + 4 (half 0), py0 + 8, py0 + 12 (half 1)
+    const float pfx = (float)px;
+    const float yc = (float)(ty * kBlockY) + 7.5f;
+    const float ylane = (float)(lane >> 4) - 7.5f;
+    const f2 yl0 = f2{ylane, ylane + 4.f}, yl1 = f2{ylane + 8.f, ylane + 12.f};
+    const bool xin = px < a.W;
+    f2 thr0 = f2{(xin && py0 < a.H) ? kAlphaMin : 2.f, (xin && py0 + 4 < a.H) ? kAlphaMin : 2.f};
+    f2 thr1 = f2{(xin && py0 + 8 < a.H) ? kAlphaMin : 2.f, (xin && py0 + 12 < a.H) ? kAlphaMin : 2.f};
+    f2 T0 = bc2(1.f), T1 = bc2(1.f);
+    f2 acc0[K], acc1[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) acc0[k] = acc1[k] = bc2(0.f);
+    uint2 range = ranges[tile];
+    range.x = __builtin_amdgcn_readfirstlane(range.x);
+    range.y = __builtin_amdgcn_readfirstlane(range.y);
+    auto load_slot = [&](uint32_t first) { return first + lane < range.y ? upos[first + lane] : 0u; };
+    auto load_gid = [&](uint32_t first, uint32_t e) { return first + lane < range.y ? gid_by_e[e] : 0u; };
+    uint32_t e1 = 0, e2 = 0, g0 = 0, g1 = 0;
+    float fcur[K], fnxt[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) fcur[k] = fnxt[k] = 0.f;
+    if (range.x < range.y) {
+        const uint32_t e0 = load_slot(range.x);
+        g0 = load_gid(range.x, e0);
+        issue_raw_lds(s_raw, range.x + lane < range.y, g0 & kGidMask, splat);
+        load_feat_row(fcur, range.x + lane < range.y, g0 & kGidMask, C, c0, features);
+        e1 = load_slot(range.x + 64);
+        g1 = load_gid(range.x + 64, e1);
+        e2 = load_slot(range.x + 128);
+    }
+    for (uint32_t base = range.x; base < range.y; base += 64) {
+        // forward.cu:312-314, both halves (a half that is done alone carries w = 0 from here on)
+        if (ballot(thr0.x < 1.f || thr0.y < 1.f || thr1.x < 1.f || thr1.y < 1.f) == 0) break;
+        SplatRegs nxt;
+        const bool valid = base + lane < range.y;
+        read_raw_lds(nxt, s_raw, lane, valid, yc, false);
+        const uint64_t reach0 = ballot(valid && ((g0 >> kReachShift) & 1u));
+        const uint64_t reach1 = ballot(valid && ((g0 >> (kReachShift + 1)) & 1u));
+        // the forward's per-batch masks, over the whole batch whatever half a splat reaches
+        const uint64_t nonpd = ballot(valid && !conic_pd(nxt.geo, nxt.opc));
+        const bool cap = ballot(valid && nxt.opc.z < kInvCapFree) != 0;
+        __builtin_amdgcn_wave_barrier();
+        s_sp[lane].geo = nxt.geo;
+        s_sp[lane].opc = nxt.opc;
+        s_feat[lane].lo = make_float4(fcur[0], fcur[1], fcur[2], fcur[3]);
+        s_feat[lane].hi = make_float4(fcur[4], fcur[5], fcur[6], fcur[7]);
+        __builtin_amdgcn_wave_barrier();
+        if (base + 64 < range.y) {
+            issue_raw_lds(s_raw, base + 64 + lane < range.y, g1 & kGidMask, splat);
+            load_feat_row(fnxt, base + 64 + lane < range.y, g1 & kGidMask, C, c0, features);
+        }
+        const uint32_t g2 = load_gid(base + 128, e2);
+        const uint32_t e3 = load_slot(base + 192);
+        // one half of one splat: the forward's blend() without the colour, returning w
+        auto blend = [&](f2 &T, f2 &thr, const Falloff &f, uint32_t j, auto pwc) {
+            bool k0 = f.alpha.x >= thr.x, k1 = f.alpha.y >= thr.y;  // forward.cu:346-348 (live pixels)
+            if (decltype(pwc)::value && ((nonpd >> j) & 1)) {      // forward.cu:341-342
+                k0 = k0 && f.pw.x <= 0.0f;
+                k1 = k1 && f.pw.y <= 0.0f;
+            }
+            f2 ae = f2{k0 ? f.alpha.x : 0.f, k1 ? f.alpha.y : 0.f};
+            f2 tT = T * (bc2(1.f) - ae);  // forward.cu:349
+            if (ballot(fminf(tT.x, tT.y) < 0.0001f) != 0) {
+                // forward.cu:350-354: not blended, the pixel retires
+                const bool t0 = tT.x < 0.0001f, t1 = tT.y < 0.0001f;
+                ae = f2{t0 ? 0.f : ae.x, t1 ? 0.f : ae.y};
+                tT = f2{t0 ? T.x : tT.x, t1 ? T.y : tT.y};
+                thr = f2{t0 ? 2.f : thr.x, t1 ? 2.f : thr.y};
+            }
+            const f2 w = ae * T;  // forward.cu:357-358
+            T = tT;
+            return w;
+        };
+        auto walk = [&](auto capc, auto pwc) {
+            constexpr bool CAP = decltype(capc)::value, FOLD = !decltype(pwc)::value;
+            for (uint64_t todo = reach0 | reach1; todo != 0; todo &= todo - 1) {
+                const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+                const float4 geo = s_sp[j].geo, opc = s_sp[j].opc;
+                const float4 flo = s_feat[j].lo, fhi = s_feat[j].hi;
+                const float fj[K] = {flo.x, flo.y, flo.z, flo.w, fhi.x, fhi.y, fhi.z, fhi.w};
+                const float dx = geo.x - pfx;
+                const float pa = fmaf(geo.z * dx, dx, opc.y), pb = geo.w * dx;
+                if ((reach0 >> j) & 1) {
+                    const f2 w = blend(T0, thr0, falloff<CAP, FOLD>(geo, opc, pa, pb, yl0), j, pwc);
+#pragma unroll
+                    for (int k = 0; k < K; k++) acc0[k] = fma2(bc2(fj[k]), w, acc0[k]);
+                }
+                if ((reach1 >> j) & 1) {
+                    const f2 w = blend(T1, thr1, falloff<CAP, FOLD>(geo, opc, pa, pb, yl1), j, pwc);
+#pragma unroll
+                    for (int k = 0; k < K; k++) acc1[k] = fma2(bc2(fj[k]), w, acc1[k]);
+                }
+            }
+        };
+        if (nonpd != 0) walk(std::true_type{}, std::true_type{});
+        else if (cap) walk(std::true_type{}, std::false_type{});
+        else walk(std::false_type{}, std::false_type{});
+        e1 = e2; e2 = e3;
+        g0 = g1; g1 = g2;
+#pragma unroll
+        for (int k = 0; k < K; k++) fcur[k] = fnxt[k];
+    }
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // an early exit may leave the next batch's LDS-DMA loads in flight
+    const size_t HW = (size_t)a.W * a.H;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int py = py0 + 4 * r;
+        if (xin && py < a.H) {
+            const size_t pix = (size_t)py * a.W + px;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const f2 v = r < 2 ? acc0[k] : acc1[k];
+                if (c0 + k < C) out[(size_t)(c0 + k) * HW + pix] = (r & 1) ? v.y : v.x;
+            }
+        }
+    }
+}
+
+hipError_t launch_features_forward(const Args &a, int C, GeomState g, BinningState b, ImageState img,
+                                   const float *features, float *out_image, hipStream_t s) {
+    const unsigned chunks = (unsigned)((C + kFeatureChunk - 1) / kFeatureChunk);
+    hipLaunchKernelGGL(feature_walk_kernel, dim3(a.gx * a.gy, chunks), dim3(64), 0, s, a, C, img.ranges, img.order,
+                       b.upos, b.gid_by_e, g.splat, features, out_image);
+    return hipGetLastError();
+}
+
+// Backward of one chunk: render_backward_kernel's reverse walk with the chunk's K channels in the place of the three
+// colours and no background layer -- T recovered backwards from final_T (backward.cu:503), the contributor test
+// against n_contrib, the forward's alpha and power rules, A = accum_rec . dL/dF carried as one scalar per pixel
+// (A = alpha CD + (1 - alpha) A with CD = f_i . dL/dF), dL/dalpha = T (CD - A), and the moments of u' = o G dL/dalpha
+// (uncapped o G, as backward.cu:519-551 has it) that make the geometry record of the kContribStride layout, colour
+// and depth fields zero.  One splat at a time over both halves; every splat takes the general path (0.99 cap, power
+// test where its conic is not positive definite).  Per splat the 6 moments and the K sums W_k = sum_p w dL/dF_k(p)
+// are reduced over the wave four at a time: lds_col_sum() over a column's four lanes, then the row's 16 columns by
+// four DPP steps (fixed order, no atomics); lane j of the batch then writes splat j's two records at its emission
+// slot.  GEOM = false (no geometry input requires grad): only the W_k are formed.  `accumulate` (chunks after the
+// first): the geometry record is added to the one the earlier chunks left at the slot, so the chunks' terms are
+// summed per instance in ascending chunk order; the K-float dL/df record is the chunk's alone.
+template <bool GEOM>
+__global__ __launch_bounds__(64) void feature_backward_kernel(Args a, int C, int c0, int accumulate,
+                                                              const uint2 *__restrict__ ranges,
+                                                              const uint32_t *__restrict__ order,
+                                                              const uint32_t *__restrict__ gid_by_e,
+                                                              const uint32_t *__restrict__ upos,
+                                                              const float4 *__restrict__ splat,
+                                                              const float *__restrict__ final_Ts,
+                                                              const uint32_t *__restrict__ n_contrib,
+                                                              const float *__restrict__ features,
+                                                              const float *__restrict__ dL_dF,
+                                                              float *__restrict__ contrib, float4 *__restrict__ frec) {
+    constexpr int K = kFeatureChunk;
+    constexpr int NV = (GEOM ? 6 : 0) + K, NR = (NV + 3) / 4;  // values reduced per splat, rounds of four
+    __shared__ SplatLDS s_sp[64];
+    __shared__ RawLDS s_raw;
+    __shared__ FeatRow s_feat[64];
+    __shared__ float s_red[64][4 * NR];
+    __shared__ float s_col[kColSumWords];
+    const int tile = (int)__builtin_amdgcn_readfirstlane(order[blockIdx.x]);
+    const int tx = tile % a.gx, ty = tile / a.gx;
+    const int lane = threadIdx.x;
+    const int px = tx * kBlockX + (lane & 15);
+    const int py0 = ty * kBlockY + (lane >> 4);
+    const float pfx = (float)px;
+    const size_t HW = (size_t)a.W * a.H;
+    uint2 range = ranges[tile];
+    range.x = __builtin_amdgcn_readfirstlane(range.x);
+    range.y = __builtin_amdgcn_readfirstlane(range.y);
+    if (range.y <= range.x) return;
+    const float ylane = (float)(lane >> 4) - 7.5f;
+    const f2 yl[2] = {f2{ylane, ylane + 4.f}, f2{ylane + 8.f, ylane + 12.f}};
+    const f2 yl2[2] = {yl[0] * yl[0], yl[1] * yl[1]};
+    const float yc = (float)(ty * kBlockY) + 7.5f;
+
+    f2 T[2], A[2] = {bc2(0.f), bc2(0.f)}, dF[2][K];
+    uint32_t lastc[4];
+    uint32_t max_last = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int py = py0 + 4 * r;
+        const bool inside = px < a.W && py < a.H;
+        const size_t pix = (size_t)py * a.W + px;
+        const float tf = inside ? final_Ts[pix] : 0.f;
+        lastc[r] = inside ? n_contrib[pix] : 0u;
+        max_last = max(max_last, lastc[r]);
+        if (r & 1) T[r >> 1].y = tf;
+        else T[r >> 1].x = tf;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const float d = (inside && c0 + k < C) ? dL_dF[(size_t)(c0 + k) * HW + pix] : 0.f;
+            if (r & 1) dF[r >> 1][k].y = d;
+            else dF[r >> 1][k].x = d;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) max_last = max(max_last, (uint32_t)__shfl_xor((int)max_last, off));
+    max_last = __builtin_amdgcn_readfirstlane(max_last);
+
+    // splats at list position >= every pixel's n_contrib never contributed: zero records
+    const uint32_t len = range.y - range.x;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t p = max_last + lane; p < len; p += 64) {
+        const uint32_t e = upos[range.x + p];
+        if (GEOM && !accumulate) {
+            float4 *rec = reinterpret_cast<float4 *>(contrib + (size_t)e * kContribStride);
+            rec[0] = z4;
+            rec[1] = z4;
+            rec[2] = z4;
+        }
+        frec[2 * (size_t)e] = z4;
+        frec[2 * (size_t)e + 1] = z4;
+    }
+    for (int end = (int)max_last; end > 0; end -= 64) {
+        const int n = min(64, end);
+        // lane l holds list position end - 1 - l: the walk goes back to front
+        const bool valid = lane < n;
+        const uint32_t ecur = valid ? upos[range.x + (uint32_t)(end - 1 - lane)] : 0u;
+        const uint32_t ge = valid ? gid_by_e[ecur] : 0u;
+        issue_raw_lds(s_raw, valid, ge & kGidMask, splat);
+        float fl[K];
+        load_feat_row(fl, valid, ge & kGidMask, C, c0, features);
+        const uint64_t reach[2] = {ballot(valid && ((ge >> kReachShift) & 1u)),
+                                   ballot(valid && ((ge >> (kReachShift + 1)) & 1u))};
+        SplatRegs nxt;
+        read_raw_lds(nxt, s_raw, lane, valid, yc, false);  // my - yc, as the forward stages it
+        const uint64_t nonpd = ballot(valid && !conic_pd(nxt.geo, nxt.opc));
+        __builtin_amdgcn_wave_barrier();
+        s_sp[lane].geo = nxt.geo;
+        s_sp[lane].opc = nxt.opc;
+        s_feat[lane].lo = make_float4(fl[0], fl[1], fl[2], fl[3]);
+        s_feat[lane].hi = make_float4(fl[4], fl[5], fl[6], fl[7]);
+#pragma unroll
+        for (int q = 0; q < 4 * NR; q++) s_red[lane][q] = 0.f;  // a splat reaching neither half is not walked
+        __builtin_amdgcn_wave_barrier();
+        for (uint64_t todo = reach[0] | reach[1]; todo != 0; todo &= todo - 1) {
+            const int j = __builtin_ctzll(todo);
+            const float4 geo = s_sp[j].geo, opc = s_sp[j].opc;
+            const float4 flo = s_feat[j].lo, fhi = s_feat[j].hi;
+            const float fj[K] = {flo.x, flo.y, flo.z, flo.w, fhi.x, fhi.y, fhi.z, fhi.w};
+            const float dx = geo.x - pfx;
+            const float pa = fmaf(geo.z * dx, dx, opc.y), pb = geo.w * dx;  // the forward's operands
+            const bool chk = (nonpd >> j) & 1;
+            const uint32_t contributor = (uint32_t)(end - 1 - j);
+            float lu0 = 0.f, lu1 = 0.f, lu2 = 0.f, Wk[K];
+#pragma unroll
+            for (int k = 0; k < K; k++) Wk[k] = 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                if (!((reach[h] >> j) & 1)) continue;  // alpha < 1/255 at every pixel of the half
+                const Falloff f = falloff<true, false>(geo, opc, pa, pb, yl[h]);
+                const f2 al = bc2(opc.w) * f.G;  // o G, the forward's product
+                // backward.cu:486-497: the contributor test, alpha < 1/255 and power > 0 skip
+                bool k0 = al.x >= kAlphaMin && contributor < lastc[2 * h];
+                bool k1 = al.y >= kAlphaMin && contributor < lastc[2 * h + 1];
+                if (chk) {
+                    k0 = k0 && f.pw.x <= 0.0f;
+                    k1 = k1 && f.pw.y <= 0.0f;
+                }
+                const f2 ale = f2{k0 ? al.x : 0.f, k1 ? al.y : 0.f};
+                const f2 ae = f2{fminf(0.99f, ale.x), fminf(0.99f, ale.y)};
+                const f2 om = bc2(1.f) - ae;
+                const f2 Tn = T[h] * f2{__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};  // backward.cu:503
+                T[h] = Tn;
+                const f2 w = ae * Tn;
+#pragma unroll
+                for (int k = 0; k < K; k++) Wk[k] += hsum(w * dF[h][k]);
+                if (GEOM) {
+                    f2 diff = -A[h];
+#pragma unroll
+                    for (int k = 0; k < K; k++) diff = fma2(bc2(fj[k]), dF[h][k], diff);  // f . dL/dF - accum_rec . dL/dF
+                    A[h] = fma2(ae, diff, A[h]);
+                    const f2 u = (ale * Tn) * diff;  // o G dL/dalpha
+                    lu0 += hsum(u);
+                    lu1 += hsum(u * yl[h]);
+                    lu2 += hsum(u * yl2[h]);
+                }
+            }
+            float v[4 * NR];
+#pragma unroll
+            for (int q = 0; q < 4 * NR; q++) v[q] = 0.f;
+            if (GEOM) {
+                v[0] = lu0; v[1] = dx * lu0; v[2] = lu1; v[3] = dx * dx * lu0; v[4] = dx * lu1; v[5] = lu2;
+            }
+#pragma unroll
+            for (int k = 0; k < K; k++) v[(GEOM ? 6 : 0) + k] = Wk[k];
+#pragma unroll
+            for (int r = 0; r < NR; r++) {
+                // value 4 r + g summed over the wave, on every lane of row g
+                float x = lds_col_sum(s_col, lane, v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+                x += dpp<0xB1>(x);   // quad_perm [1, 0, 3, 2]
+                x += dpp<0x4E>(x);   // quad_perm [2, 3, 0, 1]
+                x += dpp<0x141>(x);  // row_half_mirror
+                x += dpp<0x140>(x);  // row_mirror
+                if ((lane & 15) == 0) s_red[j][4 * r + (lane >> 4)] = x;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (valid) {
+            float r[4 * NR];
+#pragma unroll
+            for (int q = 0; q < 4 * NR; q++) r[q] = s_red[lane][q];
+            if (GEOM) {
+                // the y moments moved from the tile's centre row to the splat's: dy = my_l - yl, and the division
+                // by o (the moments were taken on u' = o u), as render_backward_kernel writes its record
+                const float my_l = s_sp[lane].geo.y, io = s_sp[lane].opc.z;
+                const float s_u = r[0], s_dxu = r[1], s_uyl = r[2], s_dx2u = r[3], s_dxuyl = r[4], s_uyl2 = r[5];
+                const float v2 = my_l * s_u - s_uyl;                   // S u dy
+                const float v4 = my_l * s_dxu - s_dxuyl;               // S dx u dy
+                const float v5 = my_l * v2 - (my_l * s_uyl - s_uyl2);  // S u dy^2
+                float4 r0 = make_float4(s_u * io, s_dxu * io, v2 * io, s_dx2u * io);
+                float4 r1 = make_float4(v4 * io, v5 * io, 0.f, 0.f);
+                float4 *rec = reinterpret_cast<float4 *>(contrib + (size_t)ecur * kContribStride);
+                if (accumulate) {
+                    const float4 p0 = rec[0], p1 = rec[1];
+                    r0 = make_float4(p0.x + r0.x, p0.y + r0.y, p0.z + r0.z, p0.w + r0.w);
+                    r1 = make_float4(p1.x + r1.x, p1.y + r1.y, 0.f, 0.f);
+                }
+                rec[0] = r0;
+                rec[1] = r1;
+                rec[2] = z4;
+            }
+            constexpr int o = GEOM ? 6 : 0;
+            frec[2 * (size_t)ecur] = make_float4(r[o], r[o + 1], r[o + 2], r[o + 3]);
+            frec[2 * (size_t)ecur + 1] = make_float4(r[o + 4], r[o + 5], r[o + 6], r[o + 7]);
+        }
+        __builtin_amdgcn_wave_barrier();  // the next batch restages s_sp / s_red
+    }
+}
+
+// dL/df of one chunk per Gaussian: importance_segments_kernel / importance_finish_kernel with K adds for the
+// operators.  One lane per emission slot, a segmented inclusive scan over the wave's 64 slots by DPP moves, a
+// Gaussian's consecutive slots being one segment.  A segment that is a whole Gaussian is written out; a piece
+// continuing from the previous wave goes to part[w][0], one that starts a Gaussian and continues into the next wave
+// to part[w][1] (two float4 each); e_first[g] = the Gaussian's first slot.
+template <int CTRL, int RM>
+__device__ __forceinline__ void feat_scan_step(float (&v)[kFeatureChunk], bool &f) {
+    const bool fu = __builtin_amdgcn_update_dpp(0, (int)f, CTRL, RM, 0xF, false) != 0;
+    float up[kFeatureChunk];
+#pragma unroll
+    for (int k = 0; k < kFeatureChunk; k++) up[k] = dpp_rows<CTRL, RM>(v[k]);
+    if (!f) {
+#pragma unroll
+        for (int k = 0; k < kFeatureChunk; k++) v[k] = __fadd_rn(v[k], up[k]);
+    }
+    f = f || fu;
+}
+__device__ __forceinline__ void store_feat_row(float *__restrict__ dL_df, uint32_t gid, int C, int c0,
+                                               const float (&v)[kFeatureChunk]) {
+#pragma unroll
+    for (int k = 0; k < kFeatureChunk; k++)
+        if (c0 + k < C) dL_df[(size_t)gid * C + c0 + k] = v[k];
+}
+__global__ __launch_bounds__(256) void feature_segments_kernel(const uint32_t *__restrict__ n_dev,
+                                                               const uint32_t *__restrict__ gid_by_e,
+                                                               const float4 *__restrict__ frec, int C, int c0,
+                                                               float *__restrict__ dL_df, float4 *__restrict__ part,
+                                                               uint32_t *__restrict__ e_first) {
+    constexpr int K = kFeatureChunk;
+    const int n = (int)__builtin_amdgcn_readfirstlane(*n_dev);
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w * 64 >= n) return;
+    const int e = w * 64 + lane;
+    const bool valid = e < n;
+    const uint32_t key = valid ? gid_by_e[e] & kGidMask : 0xFFFFFFFFu;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 lo = valid ? frec[2 * (size_t)e] : z4, hi = valid ? frec[2 * (size_t)e + 1] : z4;
+    float v[K] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t kp = __shfl_up(key, 1), kn = __shfl_down(key, 1);
+    if (lane == 0) kp = e > 0 ? gid_by_e[e - 1] & kGidMask : 0xFFFFFFFFu;
+    if (lane == 63) kn = e + 1 < n ? gid_by_e[e + 1] & kGidMask : 0xFFFFFFFFu;
+    const bool head = valid && key != kp;
+    const bool tail = valid && key != kn;
+    if (head) e_first[key] = (uint32_t)e;
+    bool f = head || lane == 0;
+    feat_scan_step<0x111, 0xF>(v, f);  // row_shr:1
+    feat_scan_step<0x112, 0xF>(v, f);  // row_shr:2
+    feat_scan_step<0x114, 0xF>(v, f);  // row_shr:4
+    feat_scan_step<0x118, 0xF>(v, f);  // row_shr:8
+    feat_scan_step<0x142, 0xA>(v, f);  // row_bcast:15 -> rows 1, 3
+    feat_scan_step<0x143, 0xC>(v, f);  // row_bcast:31 -> rows 2, 3
+    const uint64_t endm = __ballot(valid && (tail || lane == 63));
+    const int fe = __ffsll((unsigned long long)endm) - 1;  // end lane of the first piece
+    const bool head0 = __ballot(head) & 1ull;
+    if (valid && (tail || lane == 63)) {
+        const bool starts = lane != fe || head0;  // the piece starts at its Gaussian's first slot
+        if (starts && tail) {
+            store_feat_row(dL_df, key, C, c0, v);
+        } else {
+            float4 *p = part + ((size_t)w * 2 + (starts ? 1 : 0)) * 2;
+            p[0] = make_float4(v[0], v[1], v[2], v[3]);
+            p[1] = make_float4(v[4], v[5], v[6], v[7]);
+        }
+    }
+}
+// One thread per Gaussian: zeros without slots; the pieces of a Gaussian whose slots span waves in wave order,
+// part[w0][1] then part[w][0] of each following wave up to the one holding its last slot.
+__global__ __launch_bounds__(256) void feature_finish_kernel(int P, const uint32_t *__restrict__ n_inst,
+                                                             const uint32_t *__restrict__ e_first,
+                                                             const float4 *__restrict__ part, int C, int c0,
+                                                             float *__restrict__ dL_df) {
+    constexpr int K = kFeatureChunk;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= P) return;
+    const uint32_t ni = n_inst[idx];
+    float v[K] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (ni != 0) {
+        const uint32_t e0 = e_first[idx], w0 = e0 >> 6, w1 = (e0 + ni - 1) >> 6;
+        if (w0 == w1) return;  // the segments kernel wrote it
+        for (uint32_t w = w0; w <= w1; w++) {
+            const float4 *p = part + ((size_t)w * 2 + (w == w0 ? 1 : 0)) * 2;
+            const float4 l = p[0], h = p[1];
+            const float a[K] = {l.x, l.y, l.z, l.w, h.x, h.y, h.z, h.w};
+#pragma unroll
+            for (int k = 0; k < K; k++) v[k] = w == w0 ? a[k] : __fadd_rn(v[k], a[k]);
+        }
+    }
+    store_feat_row(dL_df, (uint32_t)idx, C, c0, v);
+}
+
+int feature_chunk() { return kFeatureChunk; }
+// scratch of the dL/df reduce: R records | 2 partial records per wave of 64 slots | e_first (P)
+static size_t feat_rec_bytes(int R) { return align_up((size_t)R * kFeatureChunk * sizeof(float), 256); }
+static size_t feat_part_bytes(int R) {
+    return align_up(((size_t)R + 63) / 64 * 2 * kFeatureChunk * sizeof(float), 256);
+}
+size_t features_scratch_bytes(int R, int P) {
+    return feat_rec_bytes(R) + feat_part_bytes(R) + align_up(4 * (size_t)P, 256);
+}
+// contrib (R x kContribStride floats; NULL: no geometry gradient) and fscratch (features_scratch_bytes(R, P), 256-byte
+// aligned) are the caller's scratch; every element of dL_df (P x C) is written.  R > 0.
+hipError_t launch_features_backward(const Args &a, int C, int R, GeomState g, BinningState b, ImageState img,
+                                    const float *features, const float *dL_dF, float *contrib, char *fscratch,
+                                    float *dL_df, hipStream_t s) {
+    const size_t nw = ((size_t)R + 63) / 64;
+    float4 *frec = (float4 *)fscratch;
+    float4 *part = (float4 *)(fscratch + feat_rec_bytes(R));
+    uint32_t *e_first = (uint32_t *)((char *)part + feat_part_bytes(R));
+    for (int c0 = 0; c0 < C; c0 += kFeatureChunk) {
+        const auto kernel = contrib ? feature_backward_kernel<true> : feature_backward_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(a.gx * a.gy), dim3(64), 0, s, a, C, c0, c0 > 0 ? 1 : 0, img.ranges, img.order,
+                           b.gid_by_e, b.upos, g.splat, img.final_T, img.n_contrib, features, dL_dF, contrib, frec);
+        hipLaunchKernelGGL(feature_segments_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, b.scratch,
+                           b.gid_by_e, (const float4 *)frec, C, c0, dL_df, part, e_first);
+        hipLaunchKernelGGL(feature_finish_kernel, dim3((a.P + 255) / 256), dim3(256), 0, s, a.P, g.n_inst, e_first,
+                           (const float4 *)part, C, c0, dL_df);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace gs4d

@@ -526,6 +526,7 @@ static int DebugBackwardOccupancy(bool depth, bool abs) {
 
 // importance_glue.cpp, compiled into this module: the opt-in blend-weight importance binding
 void bind_importance(pybind11::module_ &m);
+void bind_features(pybind11::module_ &m);
 
 PYBIND11_MODULE(_C, m) {
     m.def("rasterize_gaussians", &RasterizeGaussians);
@@ -543,6 +544,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("debug_tile_lists", &DebugTileLists);
     m.def("alpha_image", &AlphaImage);
     bind_importance(m);  // importance_glue.cpp: gaussian_importance
+    bind_features(m);    // features_glue.cpp: rasterize_features, rasterize_features_backward, FEATURE_CHUNK
     m.def("mark_visible", &MarkVisible);
     m.def("set_profiling", [](int level) { gs4d_set_profiling(level); });
     m.def("last_timings", &last_timings);

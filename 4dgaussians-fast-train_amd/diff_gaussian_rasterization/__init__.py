@@ -21,7 +21,11 @@ carries that factor's gradient into the covariance; radii and the binning do not
 makes raster_settings' viewmatrix, projmatrix and campos inputs of the same Function, so the ones that require grad
 receive dL/dviewmatrix, dL/dprojmatrix and dL/dcampos (pose refinement; gsplat's viewmats.grad): the forward is
 unchanged and the backward runs _C.rasterize_gaussians_backward_camera, whose other gradients are bit for bit
-those of the flag-off call.  Beside the Functions, gaussian_importance(...) runs one forward without a graph and
+those of the flag-off call.  A sixth, features=F with a (P, C) float32 tensor, is one more input of the same Function:
+the feature image (C, H, W), sum_i w_i f_i with the forward's blend weights and no background, is appended as the last
+output (_C.rasterize_features, one more walk over the state the forward left) and its gradient reaches F and the
+geometry inputs through _C.rasterize_features_backward; the other outputs and their backward keep their bits.  Beside
+the Functions, gaussian_importance(...) runs one forward without a graph and
 returns what each Gaussian deposited in it: per Gaussian the sum and the maximum of its blend weights alpha * T and the
 number of pixels it reached (the scores score-based pruning ranks by).  The compute runs in libgs4d (HIP
 kernels for gfx950) through the `_C` binding built in-tree by build_ext.py; importing this package
@@ -73,15 +77,35 @@ def _invoke(fn, args, debug, dump_name, stage):
         raise
 
 
+def _check_features(features, means3D, camera_grad):
+    if camera_grad:
+        raise ValueError("features: the feature image has no camera gradient; camera_grad=True is not supported with it")
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.dtype != torch.float32:
+        raise ValueError("features must be a 2-D float32 tensor (P, C)")
+    if features.shape[0] != means3D.shape[0]:
+        raise ValueError(f"features must have one row per Gaussian: {features.shape[0]} rows for {means3D.shape[0]}")
+    if features.shape[1] == 0:
+        raise ValueError("features must have at least one channel (C >= 1)")
+    if features.device != means3D.device:
+        raise ValueError("features must be on the means' device")
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, depth_grad=False, alpha=False, absgrad=False, antialiasing=False,
-                        camera_grad=False):
+                        camera_grad=False, features=None):
     """(color, radii, depth), or with alpha=True (color, radii, depth, alpha).  absgrad=True: the backward also
     assigns `means2D.absgrad` (P, 3): per Gaussian the sum over its pixels of |the pixel's term of means2D.grad|
     in x and y (column 2 is 0), where means2D.grad holds the signed sum.  antialiasing=True: the footprint-
     compensated opacity (module docstring) is blended, through the same Function.  camera_grad=True:
-    raster_settings.viewmatrix / .projmatrix / .campos follow the switch as inputs and receive their gradients."""
+    raster_settings.viewmatrix / .projmatrix / .campos follow the switch as inputs and receive their gradients.
+    features (P, C) float32: the feature image (C, H, W), sum_i w_i f_i with the forward's weights and no
+    background, is appended as the last output; the other outputs keep their bits.  Its gradient reaches `features`
+    and the geometry inputs; `means2D.absgrad` stays the colour path's alone.  ValueError with camera_grad=True."""
     fn = _FUNCTIONS[bool(depth_grad), bool(alpha), bool(absgrad)]
+    if features is not None:  # the features ride the same Function as one more input after the switch
+        _check_features(features, means3D, camera_grad)
+        return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                        raster_settings, bool(antialiasing), features)
     if camera_grad:
         s = raster_settings
         return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -98,8 +122,11 @@ def _zero_image(channels, s, like):
 
 
 def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-             raster_settings, antialiasing=False, *camera):
-    # camera: (viewmatrix, projmatrix, campos), raster_settings' own tensors as inputs of the Function (camera_grad)
+             raster_settings, antialiasing=False, *extra):
+    # extra: (viewmatrix, projmatrix, campos), raster_settings' own tensors as inputs of the Function (camera_grad),
+    # or (features,), the rows of the opt-in feature image
+    camera = extra if len(extra) == 3 else ()
+    features = extra[0] if len(extra) == 1 else None
     depth_grad, alpha, absgrad = variant
     s = raster_settings
     # positional order of _C.rasterize_gaussians (rasterize_points.h:18-38)
@@ -113,8 +140,9 @@ def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scal
         num_rendered, color, depth, radii, geom_buf, binning_buf, img_buf = _invoke(
             _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
     ctx.antialiasing = bool(antialiasing)
-    ctx.aa_input = len(camera) > 0 or bool(antialiasing)  # the switch was an input of the Function
+    ctx.aa_input = len(extra) > 0 or bool(antialiasing)  # the switch was an input of the Function
     ctx.camera_grad = len(camera) > 0
+    ctx.has_features = features is not None
     ctx.variant = variant
     ctx.raster_settings = s
     ctx.num_rendered = num_rendered
@@ -123,23 +151,65 @@ def _forward(ctx, variant, means3D, means2D, sh, colors_precomp, opacities, scal
     ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf,
-                          binning_buf, img_buf, *((opacities,) if antialiasing or camera else ()))
+                          binning_buf, img_buf, *((opacities,) if antialiasing or camera else ()),
+                          *((features,) if features is not None else ()))
     if absgrad:
         ctx.absgrad_target = means2D  # the caller's tensor: the backward assigns its .absgrad
+    feature_image = ()
+    if features is not None:  # one more walk over the state the forward left, which it does not change
+        if means3D.shape[0] == 0:
+            feature_image = (_zero_image(features.shape[1], s, means3D),)
+        else:
+            feature_image = (_C.rasterize_features(features, geom_buf, num_rendered, binning_buf, img_buf,
+                                                   means3D.shape[0], s.image_height, s.image_width),)
     if not alpha:
-        return color, radii, depth
+        return (color, radii, depth) + feature_image
     if means3D.shape[0] == 0:  # nothing was drawn and there is no image state to read
         alpha_image = _zero_image(1, s, means3D)
     else:
         alpha_image = _C.alpha_image(img_buf, s.image_height, s.image_width)
-    return color, radii, depth, alpha_image
+    return (color, radii, depth, alpha_image) + feature_image
 
 
-def _backward(ctx, grad_out_color, grad_depth, grad_alpha):
+def _features_backward(ctx, grad_features):
+    """The feature image's gradients: (g_means3D, g_means2D, g_opacities, g_scales, g_rotations, g_cov3D), each None
+    when no geometry input requires grad (the entry then skips the geometry stages), and g_features."""
+    s = ctx.raster_settings
+    _, means3D, scales, rotations, cov3Ds_precomp, radii, _, geom_buf, binning_buf, img_buf = ctx.saved_tensors[:10]
+    features = ctx.saved_tensors[-1]
+    if means3D.shape[0] == 0:
+        return (None,) * 6 + (torch.zeros_like(features),)
+    geometry = any(ctx.needs_input_grad[i] for i in (0, 1, 4, 5, 6, 7))
+    opacities = ctx.saved_tensors[10] if ctx.antialiasing else torch.empty(0, dtype=torch.float32, device=means3D.device)
+    g_feat, g_means2D, g_opac, g_means3D, g_cov3D, g_scales, g_rot = _C.rasterize_features_backward(
+        features, grad_features, means3D, radii, scales, rotations, s.scale_modifier, cov3Ds_precomp, s.viewmatrix,
+        s.projmatrix, s.tanfovx, s.tanfovy, geom_buf, ctx.num_rendered, binning_buf, img_buf, opacities,
+        ctx.antialiasing, geometry)
+    if not geometry:
+        return (None,) * 6 + (g_feat,)
+    return g_means3D, g_means2D, g_opac, g_scales, g_rot, g_cov3D, g_feat
+
+
+def _backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_features=None):
+    if not ctx.variant[0]:  # depth_grad off: no gradient flows from the depth image, like the reference (:100-101)
+        grad_depth = None
+    if ctx.has_features:  # camera_grad is excluded with features: the inputs end (..., switch, features)
+        base = (None,) * 9
+        if not (grad_out_color is None and grad_depth is None and grad_alpha is None):
+            base = _backward_images(ctx, grad_out_color, grad_depth, grad_alpha)[:9]
+        if grad_features is None:
+            return base + (None, None)
+        f3, f2, fo, fs, fr, fc, g_feat = _features_backward(ctx, grad_features)
+        add = lambda a, b: b if a is None else (a if b is None else a + b)
+        g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3D = base[:8]
+        return (add(g_means3D, f3), add(g_means2D, f2), g_sh, g_colors, add(g_opacities, fo), add(g_scales, fs),
+                add(g_rotations, fr), add(g_cov3D, fc), None, None, g_feat if ctx.needs_input_grad[10] else None)
+    return _backward_images(ctx, grad_out_color, grad_depth, grad_alpha)
+
+
+def _backward_images(ctx, grad_out_color, grad_depth, grad_alpha):
     depth_grad, alpha, absgrad = ctx.variant
     s = ctx.raster_settings
-    if not depth_grad:  # no gradient flows from the depth image, exactly like the reference (:100-101)
-        grad_depth = None
     # the switch itself, when it was an input, and the three camera tensors after it
     extra = ((None,) if ctx.aa_input else ()) + ((None,) * 3 if ctx.camera_grad else ())
     if grad_out_color is None and grad_depth is None and grad_alpha is None:
@@ -191,8 +261,10 @@ def _variant(depth_grad, alpha, absgrad):
     def forward(ctx, *inputs):
         return _forward(ctx, variant, *inputs)
 
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
-        return _backward(ctx, grad_out_color, grad_depth, grad_alpha)
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, *rest):
+        # rest: the alpha image's gradient (alpha=True), then the feature image's (features given)
+        grad_alpha = rest[0] if alpha and rest else None
+        return _backward(ctx, grad_out_color, grad_depth, grad_alpha, rest[-1] if ctx.has_features else None)
 
     return staticmethod(forward), staticmethod(backward)
 
@@ -301,7 +373,7 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, features=None):
         # argument exclusivity rules and messages of the reference (:191-195)
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -312,4 +384,5 @@ class GaussianRasterizer(nn.Module):
                                    _empty_if_none(scales), _empty_if_none(rotations), _empty_if_none(cov3D_precomp),
                                    self.raster_settings, depth_grad=self.depth_grad, alpha=self.alpha,
                                    absgrad=self.absgrad, antialiasing=self.antialiasing,
-                                   **({"camera_grad": True} if self.camera_grad else {}))
+                                   **({"camera_grad": True} if self.camera_grad else {}),
+                                   **({"features": features} if features is not None else {}))

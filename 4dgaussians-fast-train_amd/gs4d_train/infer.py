@@ -170,18 +170,27 @@ def _raster_settings(camera, state, bg, scaling_modifier=1.0, camera_tensors=Non
 
 
 @torch.no_grad()
-def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False, camera_tensors=None):
+def render_view(camera, state, bg, scaling_modifier=1.0, antialiasing=False, camera_tensors=None, features=None):
     """render()'s dict (gaussian_renderer/__init__.py:130-138) for a captured model, through the same rasterizer.
     antialiasing: render()'s switch; a model trained with it on is rendered with it on.  camera_tensors: render()'s
-    (viewmatrix, projmatrix, campos) in place of the camera's own, e.g. a refined pose (PoseRefiner.tensors)."""
+    (viewmatrix, projmatrix, campos) in place of the camera's own, e.g. a refined pose (PoseRefiner.tensors).
+    features: render()'s (P, C) rows, or a callable of the deformed means; the dict gains "features" (C, H, W), the
+    forward pass only."""
     import diff_gaussian_rasterization as dgr
     settings = _raster_settings(camera, state, bg, scaling_modifier, camera_tensors)
     m3, sc, rot, op, sh = state_at_time(state, camera.time, activate=True)
-    image, radii, depth = dgr.GaussianRasterizer(raster_settings=settings, antialiasing=antialiasing)(
+    extra = {}
+    if features is not None:
+        extra["features"] = features(m3) if callable(features) else features
+    out = dgr.GaussianRasterizer(raster_settings=settings, antialiasing=antialiasing)(
         means3D=m3, means2D=state.zero_points, shs=sh, colors_precomp=None, opacities=op, scales=sc, rotations=rot,
-        cov3D_precomp=None)
-    return {"render": image, "viewspace_points": state.zero_points, "visibility_filter": radii > 0, "radii": radii,
-            "depth": depth}
+        cov3D_precomp=None, **extra)
+    image, radii, depth = out[:3]
+    pkg = {"render": image, "viewspace_points": state.zero_points, "visibility_filter": radii > 0, "radii": radii,
+           "depth": depth}
+    if features is not None:
+        pkg["features"] = out[3]
+    return pkg
 
 
 @torch.no_grad()

@@ -101,8 +101,11 @@ class RenderPackage(dict):
 
 
 def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False,
-           alpha=False, absgrad=False, antialiasing=False, camera_grad=False, camera_tensors=None):
-    """camera_grad=True (opt-in): the backward also differentiates the image with respect to the camera; the view
+           alpha=False, absgrad=False, antialiasing=False, camera_grad=False, camera_tensors=None, features=None):
+    """features (opt-in): a (P, C) float32 tensor, or a callable taking the deformed means (P, 3) and returning one;
+    the package gains "features" (C, H, W), the rows blended with the image's own weights alpha * T (no background, not
+    normalised: divide by "alpha" for the mean), differentiable to the rows and to the geometry.  Not with camera_grad.
+    camera_grad=True (opt-in): the backward also differentiates the image with respect to the camera; the view
     matrix, the full projection and the camera centre that require grad receive their gradients (pose refinement).
     camera_tensors=(viewmatrix, projmatrix, campos), device tensors, stand in for the camera's own three -- a
     gs4d_train.pose.PoseRefiner's, typically; they are used with or without camera_grad.
@@ -155,10 +158,17 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
         sc = pc.scaling_activation(sc)
         rot = pc.rotation_activation(rot)
         op = pc.opacity_activation(op)
-    out = rasterizer(means3D=m3, means2D=screenspace_points, shs=sh, colors_precomp=None,
-                     opacities=op, scales=sc, rotations=rot, cov3D_precomp=None)
+    if features is None:
+        out = rasterizer(means3D=m3, means2D=screenspace_points, shs=sh, colors_precomp=None,
+                         opacities=op, scales=sc, rotations=rot, cov3D_precomp=None)
+    else:
+        rows = features(m3) if callable(features) else features
+        out = rasterizer(means3D=m3, means2D=screenspace_points, shs=sh, colors_precomp=None,
+                         opacities=op, scales=sc, rotations=rot, cov3D_precomp=None, features=rows)
     image, radii, depth = out[:3]
+    extra = {}
     if alpha:
-        return RenderPackage(render=image, viewspace_points=screenspace_points, radii=radii, depth=depth,
-                             alpha=out[3])
-    return RenderPackage(render=image, viewspace_points=screenspace_points, radii=radii, depth=depth)
+        extra["alpha"] = out[3]
+    if features is not None:
+        extra["features"] = out[-1]
+    return RenderPackage(render=image, viewspace_points=screenspace_points, radii=radii, depth=depth, **extra)

@@ -280,6 +280,47 @@ int gs4d_importance(int P, int width, int height, int num_rendered,
                     float *weight_sum, float *weight_max, int32_t *pixel_count,
                     gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream);
 
+/* N-channel feature rendering over a finished forward (no reference counterpart; opt-in).  `features` is P x C
+ * fp32 (device, contiguous, any sign), C >= 1.  gs4d_features_forward reads the state a finished gs4d_forward / _ex /
+ * _aa left in its three buffers (carved as gs4d_importance carves them), replays the blend walk and writes
+ *   out_image[c][p] = sum_i w_ip features[i][c]      (C x height x width)
+ * with w_ip = alpha_ip T_ip the forward's own weights under the forward's own rules (see gs4d_importance); after
+ * gs4d_forward_aa they are the antialiased forward's.  There is no background term and no normalisation.  A channel
+ * is accumulated as the forward accumulates a colour channel (fma(f, w, acc) in list order), so it is bit for bit
+ * the colour the forward blends for colors_precomp = that column over a zero background.  The walk takes
+ * gs4d_feature_chunk() channels at a time (chunks are a grid dimension) and reads the rows in place: it takes no
+ * scratch, and scratch_alloc / scratch_ctx are not called (they may be NULL).  num_rendered == 0 writes a zero image.
+ *
+ * gs4d_features_backward takes the forward's geometry inputs and camera as gs4d_backward_aa does, plus `features`
+ * and dL_dfeature_image (C x height x width), and writes
+ *   dL_dfeatures[i][c] = sum_p w_ip dL_dfeature_image[c][p]      (P x C, every element)
+ * and, through dL/dalpha_ip = sum_c dL/dF_c(p) (T_ip f_ic - S_ipc / (1 - alpha_ip)), S_ipc = sum_{j>i} w_jp f_jc,
+ * and the chain of gs4d_backward (the 0.99 cap and, with `antialiasing`, the factor's gradient included), the
+ * geometry gradients dL_dmean2D (P x 3), dL_dopacity (P), dL_dmean3D (P x 3), dL_dcov3D (P x 6), dL_dscale (P x 3)
+ * and dL_drot (P x 4), every element.  A NULL dL_dmean2D asks for dL_dfeatures alone: the geometry records, their
+ * reduction and the per-Gaussian stage are skipped and no geometry output is touched.  `radii` may be NULL (the
+ * forward's internal radii).  Sums run in a fixed order without float atomics (per wave, per emission slot, then a
+ * Gaussian's slots in order; several chunks add their geometry terms per instance in ascending chunk order): two
+ * calls give the same bits.  Nothing synchronises; all launches go to `stream`; the forward's buffers are left as
+ * they are.  The scratch (per-instance records: gs4d_feature_chunk() + 12 floats each, whatever C) comes from
+ * scratch_alloc and must stay valid until the stream has run the launches.
+ * Status (both): GS4D_OK at once for P == 0; GS4D_ERR_ARG (message beginning "features:") for C < 1, P < 0,
+ * num_rendered < 0, an empty image, or with P > 0 a NULL buffer (binning_buffer may be NULL when num_rendered == 0),
+ * input or required output; the backward also for a NULL allocator, and GS4D_ERR_ALLOC when it returns NULL. */
+int gs4d_feature_chunk(void);
+int gs4d_features_forward(int P, int C, int width, int height, int num_rendered, const char *geometry_buffer,
+                          const char *binning_buffer, const char *image_buffer, const float *features,
+                          float *out_image, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream);
+int gs4d_features_backward(int P, int C, int num_rendered, int width, int height, const float *means3D,
+                           const float *scales, float scale_modifier, const float *rotations,
+                           const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix,
+                           float tan_fovx, float tan_fovy, const int *radii, char *geom_buffer, char *binning_buffer,
+                           char *image_buffer, const float *features, const float *dL_dfeature_image,
+                           float *dL_dfeatures, float *dL_dmean2D, float *dL_dopacity, float *dL_dmean3D,
+                           float *dL_dcov3D, float *dL_dscale, float *dL_drot, gs4d_alloc_fn scratch_alloc,
+                           void *scratch_ctx, void *stream, int view_transposed, const float *opacities,
+                           int antialiasing);
+
 /* Replaces SimpleKNN::knn(submodules/simple-knn/simple_knn.h:14-20, simple_knn.cu:187-223), the
  * native layer behind simple_knn._C.distCUDA2 (spatial.cu:15-25, ext.cpp:15-16), which
  * scene/gaussian_model.py:148-149 uses to initialise the Gaussian scales.

@@ -756,4 +756,18 @@ int gs4d_knn_mean_dist(int P, const float *points, float *mean_dists, gs4d_alloc
     return GS4D_OK;
 }
 
+int gs4d_knn_graph(int P, int K, const float *points, int32_t *nbr_idx, float *nbr_dist2, int32_t *in_start,
+                   int32_t *in_edge, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (K < 1 || K > 16) return fail(GS4D_ERR_ARG, "knn_graph: K must be in 1..16");
+    if (P < 0 || (size_t)P * K >= ((size_t)1 << 30)) return fail(GS4D_ERR_ARG, "knn_graph: P must be >= 0 and P K below 2^30");
+    if (P == 0) return GS4D_OK;
+    if (!points || !nbr_idx || !nbr_dist2 || !in_start || !in_edge) return fail(GS4D_ERR_ARG, "knn_graph: missing buffers");
+    if (!scratch_alloc) return fail(GS4D_ERR_ARG, "knn_graph: missing the scratch allocator");
+    char *scratch = scratch_alloc(scratch_ctx, knn_graph_scratch_bytes(P, K));
+    if (!scratch) return fail(GS4D_ERR_ALLOC, "knn_graph: scratch allocation failed");
+    GS4D_HIP(launch_knn_graph(P, K, points, nbr_idx, nbr_dist2, in_start, in_edge, scratch, stream));
+    return GS4D_OK;
+}
+
 }  // extern "C"

@@ -278,6 +278,9 @@ hipError_t launch_features_backward(const Args &a, int C, int R, GeomState g, Bi
 
 size_t knn_scratch_bytes(int P);
 hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch, hipStream_t s);
+size_t knn_graph_scratch_bytes(int P, int K);
+hipError_t launch_knn_graph(int P, int K, const float *pts, int32_t *nbr_idx, float *nbr_dist2, int32_t *in_start,
+                            int32_t *in_edge, char *scratch, hipStream_t s);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

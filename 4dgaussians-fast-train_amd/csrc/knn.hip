@@ -22,6 +22,7 @@
 // with -ffp-contract=off), identically in the oracle.
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 
 #include "radix_sort.h"
 
@@ -284,7 +285,15 @@ size_t knn_scratch_bytes(int P) {
     return b + 256;
 }
 
-hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch, hipStream_t s) {
+// the stages both entries share: bounds, Morton codes, sort, boxes, sub-boxes (carved from `scratch`)
+struct KnnStages {
+    float4 *sorted;
+    uint32_t *order;
+    KnnBox *boxes, *sub;
+    int nbox;
+};
+
+static hipError_t knn_stages(int P, const float *pts, char *scratch, hipStream_t s, KnnStages *out) {
     const int nblk = sort_nblk(P, kKnnSortThreads * kKnnSortItems);
     const int nbox = (P + kKnnBox - 1) / kKnnBox;
     char *q = (char *)align_up((size_t)scratch, 256);
@@ -314,8 +323,224 @@ hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch,
     hipLaunchKernelGGL(knn_boxes_kernel, dim3(nbox), dim3(kKnnThreads), 0, s, P, pts, order[cur], sorted, boxes);
     hipLaunchKernelGGL(knn_subboxes_kernel, dim3((P + kKnnThreads - 1) / kKnnThreads), dim3(kKnnThreads), 0, s, P,
                        sorted, sub);
-    hipLaunchKernelGGL(knn_dist_kernel, dim3((P + kKnnThreads - 1) / kKnnThreads), dim3(kKnnThreads), 0, s, P, sorted,
-                       order[cur], boxes, nbox, sub, mean_dists);
+    *out = KnnStages{sorted, order[cur], boxes, sub, nbox};
+    return hipGetLastError();
+}
+
+hipError_t launch_knn(int P, const float *pts, float *mean_dists, char *scratch, hipStream_t s) {
+    KnnStages st;
+    const hipError_t e = knn_stages(P, pts, scratch, s, &st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(knn_dist_kernel, dim3((P + kKnnThreads - 1) / kKnnThreads), dim3(kKnnThreads), 0, s, P, st.sorted,
+                       st.order, st.boxes, st.nbox, st.sub, mean_dists);
+    return hipGetLastError();
+}
+
+// ---- the K-NN graph (gs4d_knn_graph): the same search keeping the K best (distance, index) pairs, and the
+// graph's transpose by a stable sort of the edge ids by target ------------------------------------------------
+
+constexpr int kKnnGraphMaxK = 16;
+
+// The K best of a lane, ascending by (squared distance, original index), in the LAST K of CAP register slots: the
+// slots before them hold (-1, -1), below every candidate, and never move, so the K-th best is always slot
+// CAP - 1 -- every index below is a compile-time constant and the list stays in registers.
+template <int CAP>
+struct KnnBest {
+    float d[CAP];
+    int id[CAP];
+    __device__ __forceinline__ void reset(int K) {
+#pragma unroll
+        for (int j = 0; j < CAP; j++) {
+            const bool live = j >= CAP - K;
+            d[j] = live ? FLT_MAX : -1.f;
+            id[j] = live ? INT_MAX : -1;
+        }
+    }
+    __device__ __forceinline__ float worst() const { return d[CAP - 1]; }
+    // update3 with the index as the tie-break: equal distances go to the lower index
+    __device__ __forceinline__ void insert(float cd, int cid) {
+#pragma unroll
+        for (int j = 0; j < CAP; j++) {
+            if (d[j] > cd || (d[j] == cd && id[j] > cid)) {
+                const float td = d[j];
+                const int ti = id[j];
+                d[j] = cd;
+                id[j] = cid;
+                cd = td;
+                cid = ti;
+            }
+        }
+    }
+};
+
+// knn_dist_kernel keeping the neighbours: the rejection radius is the K-th best among the +-K sorted neighbours;
+// a candidate's original index is read only when its distance can enter the list.
+template <int CAP>
+__global__ __launch_bounds__(kKnnThreads) void knn_graph_kernel(int P, int K, const float4 *__restrict__ sorted,
+                                                                const uint32_t *__restrict__ order,
+                                                                const KnnBox *__restrict__ boxes, int nbox,
+                                                                const KnnBox *__restrict__ sub,
+                                                                int32_t *__restrict__ nbr_idx,
+                                                                float *__restrict__ nbr_dist2) {
+    __shared__ KnnBox s_box[kKnnLdsBoxes];
+    const int idx = blockIdx.x * kKnnThreads + threadIdx.x;
+    const bool live = idx < P;
+    const float4 p = live ? sorted[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+    KnnBest<CAP> best;
+    best.reset(K);
+    if (live) {
+        for (int i = max(0, idx - K); i <= min(P - 1, idx + K); i++)
+            if (i != idx) best.insert(sqdist(p, sorted[i]), i);  // the radius needs no tie-break: any index does
+    }
+    const float reject = best.worst();
+    best.reset(K);
+    for (int b0 = 0; b0 < nbox; b0 += kKnnLdsBoxes) {
+        const int nb = min(kKnnLdsBoxes, nbox - b0);
+        __syncthreads();
+        for (int k = threadIdx.x; k < nb; k += kKnnThreads) s_box[k] = boxes[b0 + k];
+        __syncthreads();
+        if (!live) continue;
+        for (int k = 0; k < nb; k++) {
+            const float d = box_dist(s_box[k].mn, s_box[k].mx, p);
+            if (d > reject || d > best.worst()) continue;
+            const int lo = (b0 + k) * kKnnBox, hi = min(P, lo + kKnnBox);
+            for (int s0 = lo; s0 < hi; s0 += kKnnSub) {
+                const KnnBox sb = sub[s0 / kKnnSub];
+                const float ds = box_dist(sb.mn, sb.mx, p);
+                if (ds > reject || ds > best.worst()) continue;
+                const int s1 = min(hi, s0 + kKnnSub);
+                for (int i = s0; i < s1; i++) {
+                    if (i == idx) continue;
+                    const float di = sqdist(p, sorted[i]);
+                    if (di <= best.worst()) best.insert(di, (int)order[i]);
+                }
+            }
+        }
+    }
+    if (live) {
+        const size_t row = (size_t)order[idx] * K;
+#pragma unroll
+        for (int j = 0; j < CAP; j++) {
+            if (j >= CAP - K) {
+                const bool found = best.id[j] != INT_MAX;
+                nbr_idx[row + (j - (CAP - K))] = found ? best.id[j] : -1;
+                nbr_dist2[row + (j - (CAP - K))] = found ? best.d[j] : FLT_MAX;
+            }
+        }
+    }
+}
+
+// Item j of the transpose's sort = valid edge (j / Kv) K + j % Kv (Kv = min(K, P - 1): a row's valid slots come
+// first): key = its target, value = its edge id, and the sort's sharded digit histograms.
+__global__ __launch_bounds__(kKnnThreads) void knn_edge_keys_kernel(int E, int K, int Kv,
+                                                                    const int32_t *__restrict__ nbr_idx,
+                                                                    uint32_t *__restrict__ keys,
+                                                                    uint32_t *__restrict__ vals,
+                                                                    uint32_t *__restrict__ hist) {
+    __shared__ uint32_t s_hist[4][256];
+    for (int p = 0; p < 4; p++) s_hist[p][threadIdx.x] = 0;
+    __syncthreads();
+    const int j = blockIdx.x * kKnnThreads + threadIdx.x;
+    if (j < E) {
+        const uint32_t e = (uint32_t)(j / Kv) * (uint32_t)K + (uint32_t)(j % Kv);
+        const uint32_t t = (uint32_t)nbr_idx[e];
+        keys[j] = t;
+        vals[j] = e;
+#pragma unroll
+        for (int p = 0; p < 4; p++) atomicAdd(&s_hist[p][(t >> (8 * p)) & 0xFFu], 1u);
+    }
+    __syncthreads();
+    uint32_t *h = hist + (blockIdx.x % kHistShards) * (kMaxPasses * 256);
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+        if (s_hist[p][threadIdx.x]) atomicAdd(&h[p * 256 + threadIdx.x], s_hist[p][threadIdx.x]);
+}
+
+// A sorted position whose target differs from its predecessor's is the head of that target's run; the targets
+// between the two (in-degree 0) start there too, and those past the last one start at E.  in_edge = the sorted
+// edge ids, -1 past E.  One lane per slot of in_edge.
+__global__ __launch_bounds__(kKnnThreads) void knn_edge_heads_kernel(int P, int E, int slots,
+                                                                     const uint32_t *__restrict__ keys,
+                                                                     const uint32_t *__restrict__ vals,
+                                                                     int32_t *__restrict__ in_start,
+                                                                     int32_t *__restrict__ in_edge) {
+    const int j = blockIdx.x * kKnnThreads + threadIdx.x;
+    if (j < slots) in_edge[j] = j < E ? (int32_t)vals[j] : -1;
+    if (j < E) {
+        // a row of NaN coordinates finds no neighbour and leaves the key of -1: clamped, so every store stays inside
+        const int t = (int)min(keys[j], (uint32_t)(P - 1)), prev = j > 0 ? (int)min(keys[j - 1], (uint32_t)(P - 1)) : -1;
+        for (int q = prev + 1; q <= t; q++) in_start[q] = j;
+        if (j == E - 1)
+            for (int q = t + 1; q <= P; q++) in_start[q] = E;
+    }
+}
+
+static int edge_key_bits(int P) {  // the bits of P - 1, at least one
+    int bits = 1;
+    while (bits < 31 && ((uint32_t)(P - 1) >> bits)) bits++;
+    return bits;
+}
+
+size_t knn_graph_scratch_bytes(int P, int K) {
+    const size_t E = (size_t)P * std::min(K, P - 1);
+    const size_t nblk = (size_t)sort_nblk((int)E, kKnnSortThreads * kKnnSortItems);
+    size_t b = knn_scratch_bytes(P);
+    b += align_up(4 * (64 + (size_t)kHistWords + 4 * 256 * nblk), 256);  // error word | hist | look-back
+    b += 4 * align_up(4 * E, 256);                                       // keys x2, edge ids x2
+    return b + 256;
+}
+
+hipError_t launch_knn_graph(int P, int K, const float *pts, int32_t *nbr_idx, float *nbr_dist2, int32_t *in_start,
+                            int32_t *in_edge, char *scratch, hipStream_t s) {
+    KnnStages st;
+    hipError_t e = knn_stages(P, pts, scratch, s, &st);
+    if (e != hipSuccess) return e;
+    const dim3 grid((P + kKnnThreads - 1) / kKnnThreads), block(kKnnThreads);
+    if (K <= 4)
+        hipLaunchKernelGGL(knn_graph_kernel<4>, grid, block, 0, s, P, K, st.sorted, st.order, st.boxes, st.nbox, st.sub,
+                           nbr_idx, nbr_dist2);
+    else if (K <= 8)
+        hipLaunchKernelGGL(knn_graph_kernel<8>, grid, block, 0, s, P, K, st.sorted, st.order, st.boxes, st.nbox, st.sub,
+                           nbr_idx, nbr_dist2);
+    else
+        hipLaunchKernelGGL(knn_graph_kernel<kKnnGraphMaxK>, grid, block, 0, s, P, K, st.sorted, st.order, st.boxes,
+                           st.nbox, st.sub, nbr_idx, nbr_dist2);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    // ---- the transpose
+    const int Kv = std::min(K, P - 1), E = P * Kv, slots = P * K;
+    if (E == 0) {  // P == 1: no edge
+        e = hipMemsetAsync(in_start, 0, sizeof(int32_t) * ((size_t)P + 1), s);
+        if (e != hipSuccess) return e;
+        return hipMemsetAsync(in_edge, 0xFF, sizeof(int32_t) * (size_t)slots, s);
+    }
+    const int nblk = sort_nblk(E, kKnnSortThreads * kKnnSortItems);
+    char *q = (char *)align_up((size_t)scratch, 256) + align_up(knn_scratch_bytes(P), 256);
+    auto take = [&](size_t bytes) {
+        char *r = q;
+        q += align_up(bytes, 256);
+        return r;
+    };
+    const size_t zero_words = 64 + (size_t)kHistWords + 4 * 256 * (size_t)nblk;
+    uint32_t *zero = (uint32_t *)take(4 * zero_words);
+    uint32_t *keys[2] = {(uint32_t *)take(4 * (size_t)E), (uint32_t *)take(4 * (size_t)E)};
+    uint32_t *vals[2] = {(uint32_t *)take(4 * (size_t)E), (uint32_t *)take(4 * (size_t)E)};
+    uint32_t *err = zero, *hist = zero + 64, *look = zero + 64 + kHistWords;
+    e = hipMemsetAsync(zero, 0, 4 * zero_words, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(knn_edge_keys_kernel, dim3((E + kKnnThreads - 1) / kKnnThreads), block, 0, s, E, K, Kv, nbr_idx,
+                       keys[0], vals[0], hist);
+    const int npass = (edge_key_bits(P) + 7) / 8;
+    int cur = 0;
+    for (int p = 0; p < npass; p++) {  // the edge ids are no identity (Kv < K skips slots): they ride from pass 0 on
+        hipLaunchKernelGGL((onesweep_kernel<kKnnSortThreads, kKnnSortItems>), dim3(nblk), dim3(kKnnSortThreads), 0, s,
+                           keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], E, nullptr, 8 * p, hist + 256 * p,
+                           look + (size_t)p * 256 * nblk, err);
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(knn_edge_heads_kernel, dim3((slots + kKnnThreads - 1) / kKnnThreads), block, 0, s, P, E, slots,
+                       keys[cur], vals[cur], in_start, in_edge);
     return hipGetLastError();
 }
 

@@ -38,4 +38,9 @@ torch::Tensor distCUDA2(const torch::Tensor &points) {
     return means;
 }
 
-PYBIND11_MODULE(_C, m) { m.def("distCUDA2", &distCUDA2); }
+void bind_knn_graph(pybind11::module_ &m);  // knn_graph_glue.cpp
+
+PYBIND11_MODULE(_C, m) {
+    m.def("distCUDA2", &distCUDA2);
+    bind_knn_graph(m);
+}

@@ -1338,7 +1338,10 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>, torch::Tensor> voxel_dow
     return {out_p.narrow(0, 0, M).clone(), colors_out, counts.narrow(0, 0, M).clone()};
 }
 
+void bind_rigidity(pybind11::module_ &m);  // rigidity_glue.cpp
+
 PYBIND11_MODULE(_C, m) {
+    bind_rigidity(m);
     m.def("voxel_downsample", &voxel_downsample, py::arg("points"), py::arg("colors"), py::arg("voxel_size"));
     m.def("hexplane_points", &hexplane_points);
     m.def("hexplane_points_backward", &hexplane_points_backward, py::arg("dpts"), py::arg("aabb"),

@@ -44,7 +44,10 @@ def optimization_params(**over):
              antialiasing=False,
              # opt-in (pose refinement): learning rate of the per-camera pose deltas' Adam; read only when
              # train_step is given a PoseRefiner (train.py), 0 = off
-             pose_lr=0.0)
+             pose_lr=0.0,
+             # opt-in (local rigidity): weight of the isometry term between the canonical and the deformed means over
+             # a K-NN graph; read only in the fine stage and when train_step is given a rigidity.Rigidity, 0 = off
+             lambda_rigid=0.0)
     d.update(over)
     return SimpleNamespace(**d)
 

@@ -101,8 +101,11 @@ class RenderPackage(dict):
 
 
 def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, stage="fine", depth_grad=False,
-           alpha=False, absgrad=False, antialiasing=False, camera_grad=False, camera_tensors=None, features=None):
-    """features (opt-in): a (P, C) float32 tensor, or a callable taking the deformed means (P, 3) and returning one;
+           alpha=False, absgrad=False, antialiasing=False, camera_grad=False, camera_tensors=None, features=None,
+           return_means=False):
+    """return_means=True (opt-in): the package gains "means3D", the deformed means (P, 3) handed to the rasterizer, with
+    their graph attached (a 3-D term on them -- rigidity.isometry_loss -- needs no second deformation pass).
+    features (opt-in): a (P, C) float32 tensor, or a callable taking the deformed means (P, 3) and returning one;
     the package gains "features" (C, H, W), the rows blended with the image's own weights alpha * T (no background, not
     normalised: divide by "alpha" for the mean), differentiable to the rows and to the geometry.  Not with camera_grad.
     camera_grad=True (opt-in): the backward also differentiates the image with respect to the camera; the view
@@ -171,4 +174,6 @@ def render(viewpoint_camera, pc, pipe_debug, bg_color, scaling_modifier=1.0, sta
         extra["alpha"] = out[3]
     if features is not None:
         extra["features"] = out[-1]
+    if return_means:
+        extra["means3D"] = m3
     return RenderPackage(render=image, viewspace_points=screenspace_points, radii=radii, depth=depth, **extra)

@@ -113,6 +113,8 @@ def apply(model, plan: RowPlan):
     for name, attr in PARAMS.items():
         if name in new:
             setattr(model, attr, new[name])
+    # the rows changed: whatever is built per row outside the model (rigidity.Rigidity's K-NN graph) is stale
+    model.row_generation = getattr(model, "row_generation", 0) + 1
 
 
 def replace_param(model, name, tensor):

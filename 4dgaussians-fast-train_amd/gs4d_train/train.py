@@ -34,6 +34,10 @@ Pose refinement (opt-in): with a gs4d_train.pose.PoseRefiner passed as `pose` an
 rendered through the refiner's camera tensors with camera_grad=True, so the rasterizer's camera gradient reaches the
 per-camera deltas, which an Adam of their own (lr = opt.pose_lr) steps after the Gaussians' optimizer.  The deltas'
 gradients are not reduced across ranks, so a refiner does not combine with data_parallel.
+
+Local rigidity (opt-in): with a gs4d_train.rigidity.Rigidity passed as `rigidity` and opt.lambda_rigid != 0, the fine
+stage adds lambda_rigid * the isometry term between the canonical means and each view's deformed means over an exact
+K-NN graph of the canonical means (rigidity.py); the views are rendered with return_means=True for it.
 """
 import functools
 
@@ -53,7 +57,7 @@ def depth_l1(depth, gt_depth):
 
 
 def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine", fused_loss=None,
-               data_parallel=False, render_fn=None, pose=None):
+               data_parallel=False, render_fn=None, pose=None, rigidity=None):
     """views: list of (camera, gt_image (3, H, W)), (camera, gt_image, gt_depth (1, H, W) or (H, W)) or
     (camera, gt_image, gt_depth or None, gt_mask (1, H, W) or (H, W), floats in [0, 1]); the depth is read only
     when opt.lambda_depth != 0 and the mask only when opt.lambda_mask != 0.  Returns the (detached) batch loss
@@ -67,7 +71,13 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
 
     pose: a PoseRefiner; with opt.pose_lr > 0 every view is rendered with camera_grad=True and
     camera_tensors=pose.tensors(camera), and the refiner's deltas are stepped by their own Adam after the Gaussians'
-    optimizer.  With pose=None or opt.pose_lr == 0 nothing of this runs."""
+    optimizer.  With pose=None or opt.pose_lr == 0 nothing of this runs.
+
+    rigidity: a gs4d_train.rigidity.Rigidity; with opt.lambda_rigid != 0, in the fine stage, every view is rendered
+    with return_means=True and the step adds lambda_rigid * isometry(get_xyz, means3D(t)) per view, scaled like the
+    depth term, over the graph rigidity.graph_for(gaussians, iteration) gives (asked once, before the renders; a
+    densification inside the step makes it rebuild at the next one).  The term reads the render's own deformed means:
+    no second deformation pass.  With rigidity=None or opt.lambda_rigid == 0 nothing of this runs."""
     if render_fn is None:
         from .render import render as render_fn
     posing = pose is not None and float(getattr(opt, "pose_lr", 0.0)) > 0.0
@@ -94,6 +104,12 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
         render_fn = functools.partial(render_fn, absgrad=True)
     if bool(getattr(opt, "antialiasing", False)):
         render_fn = functools.partial(render_fn, antialiasing=True)
+    lambda_rigid = float(getattr(opt, "lambda_rigid", 0.0))
+    rigid_graph = None
+    if lambda_rigid != 0 and rigidity is not None and stage == "fine":
+        rigid_graph = rigidity.graph_for(gaussians, iteration)
+        render_fn = functools.partial(render_fn, return_means=True)
+    means_list = []  # the views' deformed means, when the rigidity term is on
     for v in mine:
         cam, gt = views[v][0], views[v][1]
         has_depth = lambda_depth != 0 and len(views[v]) > 2 and views[v][2] is not None
@@ -110,6 +126,11 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
             gt_depths.append(views[v][2])
         else:
             pkg = render_fn(cam, gaussians, False, background, stage=stage)
+        if rigid_graph is not None:
+            if "means3D" not in pkg:
+                raise RuntimeError("opt.lambda_rigid: render_fn's package carries no \"means3D\"; render_fn must honour "
+                                   "return_means=True (gs4d_train.render.render does)")
+            means_list.append(pkg["means3D"])
         images.append(pkg["render"].unsqueeze(0))
         gts.append(gt.unsqueeze(0))
         radii_list.append(pkg["radii"].unsqueeze(0))
@@ -194,6 +215,28 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
                     total, _, n = depth_l1(d, gd)
                     loss = loss + total / n * (lambda_depth * scale)
                 loss = loss + (a - gm.reshape(a.shape)).abs().mean() * (lambda_mask * scale)
+    rigid_tensors, rigid_grads = [], []
+    if means_list:
+        # per view: lambda_rigid * isometry(canonical means, the view's deformed means), scaled like the depth term
+        from .rigidity import isometry_loss, isometry_loss_and_grad
+        scale = lambda_rigid * share / len(mine)
+        xyz = gaussians.get_xyz
+        if image_grad is not None:
+            # fused path: the value and both explicit gradients in one pass per view (gs4d_isometry_loss_grad)
+            xyz_grad = None
+            for m in means_list:
+                value, g_a, g_b = isometry_loss_and_grad(xyz, m, rigid_graph, scale)
+                loss = loss + value
+                if m.requires_grad:
+                    rigid_tensors.append(m)
+                    rigid_grads.append(g_b)
+                xyz_grad = g_a if xyz_grad is None else xyz_grad + g_a
+            if xyz.requires_grad:
+                rigid_tensors.append(xyz)
+                rigid_grads.append(xyz_grad)
+        else:
+            for m in means_list:
+                loss = loss + isometry_loss(xyz, m, rigid_graph) * scale
     reg_w = (hyper.time_smoothness_weight, hyper.l1_time_planes, hyper.plane_tv_weight)
     reg_scale = 1.0 / dp.world() if data_parallel else 1.0
     reg_deferred = False
@@ -212,10 +255,11 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     # a data-parallel rank with no view of the batch (len(views) < world) and no regulariser has a
     # constant loss: nothing to back-propagate, its gradients are the zeros filled in below
     if image_grad is not None:
-        if image_tensor.requires_grad and aux_tensors:
-            # one backward pass: each view's rasterizer backward takes its colour, depth and alpha gradients together
-            torch.autograd.backward([image_tensor] + depths + aux_tensors,
-                                    [image_grad] + (depth_grads or []) + aux_grads)
+        if image_tensor.requires_grad and (aux_tensors or rigid_tensors):
+            # one backward pass: each view's rasterizer backward takes its colour, depth and alpha gradients together,
+            # and the deformation the rigidity term's gradient at the deformed means with the rasterizer's
+            torch.autograd.backward([image_tensor] + depths + aux_tensors + rigid_tensors,
+                                    [image_grad] + (depth_grads or []) + aux_grads + rigid_grads)
         elif image_tensor.requires_grad and depth_grads:
             # one backward pass: each view's rasterizer backward takes its colour and depth gradients together
             torch.autograd.backward([image_tensor] + depths, [image_grad] + depth_grads)

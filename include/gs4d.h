@@ -331,6 +331,22 @@ int gs4d_features_backward(int P, int C, int num_rendered, int width, int height
 int gs4d_knn_mean_dist(int P, const float *points, float *mean_dists, gs4d_alloc_fn scratch_alloc, void *scratch_ctx,
                        void *stream);
 
+/* The exact K-nearest-neighbour graph of a cloud, with its transpose (no reference counterpart; opt-in: the
+ * local-isometry regulariser of gs4d_train.h reads it).  The search is gs4d_knn_mean_dist's, keeping the neighbours.
+ * points: P x 3 fp32 (device, contiguous); K in 1..16.
+ *   nbr_idx[i K + k], nbr_dist2[i K + k]: the K nearest OTHER points of point i (self excluded by index) and their
+ *     squared distances (dx dx + dy dy) + dz dz in fp32 without contraction, ascending by (distance, index): equal
+ *     distances go to the lower index.  Slots beyond min(K, P - 1) hold -1 and FLT_MAX.
+ *   Edge e = i K + k has target nbr_idx[e].  in_edge[in_start[t] .. in_start[t + 1]) are the ids of the valid
+ *     edges whose target is t, ascending; in_start has P + 1 entries, in_edge P K, those past in_start[P] are -1.
+ * Nothing synchronises; every launch goes to `stream`; the scratch must stay valid until the stream has run them.
+ * The result is a function of the points alone: no atomic decides an order, two calls give the same bits.
+ * Status: GS4D_OK at once for P == 0; GS4D_ERR_ARG (message beginning "knn_graph:") for K outside 1..16, P < 0,
+ * P K >= 2^30, or with P > 0 a NULL pointer or a NULL allocator, all before the allocator is asked; GS4D_ERR_ALLOC
+ * when it returns NULL. */
+int gs4d_knn_graph(int P, int K, const float *points, int32_t *nbr_idx, float *nbr_dist2, int32_t *in_start,
+                   int32_t *in_edge, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream);
+
 /* Instant4D grid pruning: replaces the Open3D voxel_down_sample call of utils/grid_pruning.py:16-41, which
  * scene/__init__.py:106-119 runs on the initial cloud in front of create_from_pcd (and so in front of
  * gs4d_knn_mean_dist).  Semantics (Open3D's PointCloud::VoxelDownSample, with a defined row order):

@@ -11,6 +11,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gs4d.h" /* gs4d_alloc_fn and the status codes (gs4d_isometry_loss_grad) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -450,6 +452,23 @@ typedef struct gs4d_deform_infer_args {
     float *means, *scales, *rot, *opac, *shs;
 } gs4d_deform_infer_args;
 int gs4d_deform_infer(const gs4d_deform_infer_args *args, void *stream);
+
+/* ---- local-isometry regulariser over a K-NN graph (no reference counterpart; opt-in; csrc/rigidity.hip).
+ * The graph is gs4d_knn_graph's (gs4d.h): nbr_idx (P x K), in_start (P + 1), in_edge (P x K).  With
+ * r(v) = sqrt(v.v + 1e-12), E = P min(K, P - 1) and Delta_e = r(xb_i - xb_j) - r(xa_i - xa_j), j = nbr_idx[e]:
+ *   *value = scale / E * sum over the valid edges e = (i, k) of w_e Delta_e^2      (weights == NULL: w = 1)
+ *   dL_dxb[i] = 2 scale / E * [ sum_k w_ik Delta_ik (xb_i - xb_j) / r_b - sum_{e = (m, k) in in(i)} w_e Delta_e (xb_m - xb_i) / r_b ]
+ *   dL_dxa[i] = the same over xa and r_a with the opposite sign.
+ * A node sums its out-edges in ascending k, then its in-edges in in_edge order; the value is summed per workgroup
+ * in a fixed tree and the workgroups' partials in fp64 in index order by a second launch: no atomics, two calls
+ * give the same bits.  Either gradient pointer may be NULL: that side is skipped, the other side's bits are
+ * unchanged.  Nothing synchronises; the scratch must stay valid until `stream` has run the two launches.
+ * Status: GS4D_OK at once for P == 0; GS4D_ERR_ARG (message beginning "isometry:") for K outside 1..16, P < 0,
+ * P K >= 2^30, or with P > 0 a NULL graph, position or value pointer or a NULL allocator, all before the allocator
+ * is asked; GS4D_ERR_ALLOC when it returns NULL. */
+int gs4d_isometry_loss_grad(int P, int K, const int32_t *nbr_idx, const int32_t *in_start, const int32_t *in_edge,
+                            const float *weights, const float *xa, const float *xb, float scale, float *value,
+                            float *dL_dxa, float *dL_dxb, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream);
 
 #ifdef __cplusplus
 }

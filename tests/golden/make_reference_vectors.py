@@ -1,7 +1,9 @@
 """Generate golden vectors by RUNNING the reference's own importable Python (this container only).
 
-The reference's CUDA rasterizer cannot be built here (no nvcc/CUB), so the parts of
-the path that exist as runnable reference Python pin the oracle:
+The reference's CUDA rasterizer cannot be built for a GPU here (no nvcc/CUB).  Its
+sources are built for the host and run by tests/golden/make_raster_reference_vectors.py, which
+records the rasterizer's and simple-knn's own outputs; this script covers the parts of the path
+that exist as runnable reference Python:
   * utils/sh_utils.py:57-112  eval_sh          -> SH -> RGB (forward.cu:20-71 restates the same
                                                    polynomial; the rasterizer adds +0.5 and clamps)
   * utils/graphics_utils.py:38-71 getWorld2View2 / getProjectionMatrix, composed as

@@ -22,9 +22,9 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ARCH = os.environ.get("GS4D_ARCH", "gfx950")
 # the train step's kernels by subsystem: train_tail.hip (losses, Adam, statistics, the small streams), ssim.hip
 # (the D-SSIM loss), the deformation MLP's mlp_*.hip, deform_infer.hip (the MLP at inference) and rigidity.hip (the
-# opt-in local-isometry regulariser), all compiled alike
+# opt-in local-isometry regulariser) and mcmc.hip (the opt-in MCMC densification strategy), all compiled alike
 TRAIN_SOURCES = ["train_tail.hip", "ssim.hip", "mlp_feature.hip", "mlp_heads_forward.hip", "mlp_heads_backward.hip", "mlp_gemm.hip",
-                 "deform_infer.hip", "rigidity.hip"]
+                 "deform_infer.hip", "rigidity.hip", "mcmc.hip"]
 HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backward.hip", "camera_grad.hip", "knn.hip", *TRAIN_SOURCES, "hexplane.hip", "capi.hip", "voxel.hip"]
 # Per-Gaussian math (K1, K8/K9) is compiled without FMA contraction: it costs nothing measurable
 # (those kernels are tiny) and keeps radii / tile rects -- discrete decisions -- bit-identical to the
@@ -32,9 +32,10 @@ HIP_SOURCES = ["preprocess.hip", "binning.hip", "render.hip", "preprocess_backwa
 # (package, pybind glue) pairs: each package gets an in-tree `_C` module over libgs4d
 BINDINGS = [("diff_gaussian_rasterization", "torch_glue.cpp"), ("simple_knn", "knn_glue.cpp"), ("gs4d_train", "train_glue.cpp")]
 # further sources of a binding's module, compiled with its glue: the opt-in importance and feature-rendering bindings
-# of the rasterizer's `_C`, the opt-in K-NN graph of simple_knn's and isometry-loss binding of the train step's
+# of the rasterizer's `_C`, the opt-in K-NN graph of simple_knn's, and the isometry-loss and MCMC bindings of the
+# train step's
 EXTRA_GLUE = {"torch_glue.cpp": ["importance_glue.cpp", "features_glue.cpp"], "knn_glue.cpp": ["knn_graph_glue.cpp"],
-              "train_glue.cpp": ["rigidity_glue.cpp"]}
+              "train_glue.cpp": ["rigidity_glue.cpp", "mcmc_glue.cpp"]}
 NO_CONTRACT = {"preprocess.hip", "preprocess_backward.hip", "camera_grad.hip", "binning.hip", "knn.hip", "voxel.hip", *TRAIN_SOURCES, "hexplane.hip"}
 # The blend kernels pack pixel pairs explicitly (ext_vector_type(2) -> v_pk_*_f32); the SLP vectorizer
 # would also pack their scalar horizontal adds, paying register moves for a v_pk_add_f32 (4 issue cycles)

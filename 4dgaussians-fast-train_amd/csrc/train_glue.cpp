@@ -1339,9 +1339,11 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>, torch::Tensor> voxel_dow
 }
 
 void bind_rigidity(pybind11::module_ &m);  // rigidity_glue.cpp
+void bind_mcmc(pybind11::module_ &m);      // mcmc_glue.cpp
 
 PYBIND11_MODULE(_C, m) {
     bind_rigidity(m);
+    bind_mcmc(m);
     m.def("voxel_downsample", &voxel_downsample, py::arg("points"), py::arg("colors"), py::arg("voxel_size"));
     m.def("hexplane_points", &hexplane_points);
     m.def("hexplane_points_backward", &hexplane_points_backward, py::arg("dpts"), py::arg("aabb"),

@@ -47,7 +47,13 @@ def optimization_params(**over):
              pose_lr=0.0,
              # opt-in (local rigidity): weight of the isometry term between the canonical and the deformed means over
              # a K-NN graph; read only in the fine stage and when train_step is given a rigidity.Rigidity, 0 = off
-             lambda_rigid=0.0)
+             lambda_rigid=0.0,
+             # opt-in (3DGS-MCMC, gs4d_train/mcmc.py): "mcmc" replaces the clone / split / prune heuristic and the opacity
+             # reset by relocation of dead Gaussians (opacity <= mcmc_min_opacity), growth by 5 % per refinement up to
+             # mcmc_cap_max, per-step position noise (mcmc_noise_lr x the position learning rate) and the opacity /
+             # scale regulariser; every draw is a function of (mcmc_seed, iteration).  "default": the reference's
+             densify_strategy="default", mcmc_cap_max=1_000_000, mcmc_noise_lr=5e5, mcmc_opacity_reg=0.01,
+             mcmc_scale_reg=0.01, mcmc_min_opacity=0.005, mcmc_seed=0)
     d.update(over)
     return SimpleNamespace(**d)
 

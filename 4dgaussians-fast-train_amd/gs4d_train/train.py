@@ -38,6 +38,13 @@ gradients are not reduced across ranks, so a refiner does not combine with data_
 Local rigidity (opt-in): with a gs4d_train.rigidity.Rigidity passed as `rigidity` and opt.lambda_rigid != 0, the fine
 stage adds lambda_rigid * the isometry term between the canonical means and each view's deformed means over an exact
 K-NN graph of the canonical means (rigidity.py); the views are rendered with return_means=True for it.
+
+MCMC densification (opt-in, 3DGS-MCMC): with opt.densify_strategy == "mcmc" the clone / split / prune heuristic, its
+statistics and the opacity reset do not run.  The step adds mcmc_opacity_reg * mean(opacity) + mcmc_scale_reg *
+mean(scale) to the loss (its gradient joins the parameters' after the backward, gs4d_train.mcmc.regulariser_and_grad),
+and after the optimizer relocates the dead Gaussians (opacity <= mcmc_min_opacity) onto live ones and grows the set by
+5 % up to mcmc_cap_max on the densification schedule, then adds the opacity-gated position noise of every step
+(gs4d_train/mcmc.py).  Every draw is a function of (mcmc_seed, iteration).
 """
 import functools
 
@@ -77,7 +84,20 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
     with return_means=True and the step adds lambda_rigid * isometry(get_xyz, means3D(t)) per view, scaled like the
     depth term, over the graph rigidity.graph_for(gaussians, iteration) gives (asked once, before the renders; a
     densification inside the step makes it rebuild at the next one).  The term reads the render's own deformed means:
-    no second deformation pass.  With rigidity=None or opt.lambda_rigid == 0 nothing of this runs."""
+    no second deformation pass.  With rigidity=None or opt.lambda_rigid == 0 nothing of this runs.
+
+    opt.densify_strategy == "mcmc": add_densification_stats, densify, prune and reset_opacity are skipped; the
+    regulariser's value joins the returned loss and its gradient the parameters' (after the backward and, in a
+    data-parallel step, after the all-reduce: it depends on the parameters alone, which every replica holds); after
+    optimizer.step(), for densify_from_iter < iteration < densify_until_iter with iteration % densification_interval
+    == 0, mcmc.relocate then mcmc.grow run, and every step ends with mcmc.inject_noise at step_scale = mcmc_noise_lr *
+    the xyz group's current learning rate.  It composes with data_parallel=True with no broadcast: the draws come from a
+    counter-based generator keyed by (opt.mcmc_seed, iteration, row), the same on every replica.  With "default" (or
+    an opt without the field) nothing of this runs."""
+    strategy = getattr(opt, "densify_strategy", "default")
+    if strategy not in ("default", "mcmc"):
+        raise ValueError(f"train_step: opt.densify_strategy must be \"default\" or \"mcmc\", got {strategy!r}")
+    mcmc_on = strategy == "mcmc"
     if render_fn is None:
         from .render import render as render_fn
     posing = pose is not None and float(getattr(opt, "pose_lr", 0.0)) > 0.0
@@ -316,8 +336,13 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
         torch.distributed.all_reduce(radii, op=torch.distributed.ReduceOp.MAX)
         torch.distributed.all_reduce(vis_i, op=torch.distributed.ReduceOp.MAX)
         visibility_filter = vis_i.bool()
+    if mcmc_on:
+        from . import mcmc
+        loss_out = loss_out + mcmc.regulariser_and_grad(gaussians, float(opt.mcmc_opacity_reg), float(opt.mcmc_scale_reg))
     with torch.no_grad():
-        if iteration < opt.densify_until_iter:
+        if mcmc_on:
+            pass  # no statistics, no clone / split / prune, no opacity reset: relocation and growth follow the optimizer
+        elif iteration < opt.densify_until_iter:
             gaussians.add_densification_stats(viewspace_grad, visibility_filter, radii)
             if stage == "coarse":
                 opacity_threshold = opt.opacity_threshold_coarse
@@ -349,6 +374,14 @@ def train_step(gaussians, views, opt, hyper, iteration, background, stage="fine"
                 pose_opt = _pose_optimizer(pose, float(opt.pose_lr))
                 pose_opt.step()
                 pose_opt.zero_grad(set_to_none=True)
+            if mcmc_on:
+                seed, min_opacity = int(opt.mcmc_seed), float(opt.mcmc_min_opacity)
+                if opt.densify_from_iter < iteration < opt.densify_until_iter and \
+                        iteration % opt.densification_interval == 0:
+                    mcmc.relocate(gaussians, seed, iteration, min_opacity)
+                    mcmc.grow(gaussians, seed, iteration, int(opt.mcmc_cap_max), min_opacity)
+                xyz_lr = next(g["lr"] for g in gaussians.optimizer.param_groups if g["name"] == "xyz")
+                mcmc.inject_noise(gaussians, float(opt.mcmc_noise_lr) * float(xyz_lr), seed, iteration)
     return loss_out[0]
 
 

@@ -470,6 +470,63 @@ int gs4d_isometry_loss_grad(int P, int K, const int32_t *nbr_idx, const int32_t 
                             const float *weights, const float *xa, const float *xb, float scale, float *value,
                             float *dL_dxa, float *dL_dxb, gs4d_alloc_fn scratch_alloc, void *scratch_ctx, void *stream);
 
+/* ---- MCMC densification (no reference counterpart; opt-in; csrc/mcmc.hip; 3DGS-MCMC, Kheradmand et al. 2024).
+ * Conventions of every entry below: nothing synchronises; a scratch block must stay valid until `stream` has run
+ * the call's launches; GS4D_ERR_ARG (message beginning "mcmc:") for a bad argument, before any launch and before
+ * the allocator is asked; GS4D_ERR_ALLOC when the allocator returns NULL; GS4D_OK at once for P == 0 (and n == 0,
+ * n_blocks == 0): nothing is read or written then.
+ *
+ * The generator is Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with
+ * key (seed & 0xffffffff, seed >> 32) and counter (j, purpose, iteration, 0): j the row or draw index, purpose
+ * GS4D_MCMC_NOISE / _RELOCATE / _GROW.  gs4d_mcmc_random_bits writes the four words of blocks 0 .. n_blocks - 1
+ * (out: 4 n_blocks words). */
+enum { GS4D_MCMC_NOISE = 0, GS4D_MCMC_RELOCATE = 1, GS4D_MCMC_GROW = 2 };
+int gs4d_mcmc_random_bits(int n_blocks, uint64_t seed, uint32_t iteration, uint32_t purpose, uint32_t *out, void *stream);
+/* n draws with replacement in proportion to opacity, exact and order-free.  opacity (P): ACTIVATED opacities.
+ * w_i = (uint64)(min(o_i, 1) 2^32) where o_i > min_opacity, else 0; S = the inclusive 64-bit prefix sums; draw d
+ * takes u = w0 | w1 << 32 of block d, t = mulhi64(u, S[P-1]) and draws[d] = the first i with S[i] > t.  counts (P):
+ * the draws per row (integer atomics).  n_drawn (nullable, one int): n, or 0 when S[P-1] == 0 (no live row): counts
+ * is then all zero and draws is not written.  Status 1 for P < 0, n < 0, min_opacity < 0 or NaN, or with P, n > 0 a
+ * NULL opacity, draws, counts or allocator.  Scratch: 8 (P + ceil(P / 256)) + 256 bytes. */
+int gs4d_mcmc_sample(int P, const float *opacity, float min_opacity, int n, uint64_t seed, uint32_t iteration,
+                     uint32_t purpose, int32_t *draws, int32_t *counts, int32_t *n_drawn, gs4d_alloc_fn scratch_alloc,
+                     void *scratch_ctx, void *stream);
+/* The sources' correction, in place on the RAW opacity (P) and scaling (P, 3) of the rows with counts[r] > 0 (the
+ * others are not written): n = min(counts[r] + 1, 51), o = sigmoid(raw o), o' = -expm1(log1p(-o) / n),
+ * D = sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1) in fp64, s' = exp(raw s) o / D, o' clamped
+ * to [min_opacity, 1 - FLT_EPSILON]; stores log(o' / (1 - o')) and log(s').  min_opacity in (0, 1). */
+int gs4d_mcmc_relocate(int P, const int32_t *counts, float min_opacity, float *opacity_raw, float *scaling_raw,
+                       void *stream);
+/* The per-step noise, one launch, xyz (P, 3) in place: x += R diag(s^2) R^T (z g step_scale) with R of the
+ * normalised raw quaternion (w, x, y, z; norm clamped at 1e-12), s = exp(raw scale),
+ * g = 1 / (1 + exp(-100 ((1 - sigmoid(raw opacity)) - 0.995))), and z = normals[r] when normals (P, 3) is given,
+ * else of block r (purpose GS4D_MCMC_NOISE): u_k = ((w_k >> 8) + 0.5) 2^-24, r0 = sqrt(-2 ln u_0),
+ * r1 = sqrt(-2 ln u_2), z = (r0 cos 2 pi u_1, r0 sin 2 pi u_1, r1 cos 2 pi u_3). */
+int gs4d_mcmc_noise(int P, float *xyz, const float *scaling_raw, const float *rotation_raw, const float *opacity_raw,
+                    float step_scale, uint64_t seed, uint32_t iteration, const float *normals, void *stream);
+/* *value = w_opacity mean(sigmoid(raw o)) + w_scale mean(exp(raw s)) (means over P and 3 P elements), and its
+ * gradient ADDED into grad_opacity (P) and grad_scaling (P, 3) (either may be NULL: skipped).  The value: a tree per
+ * workgroup of 256 rows, the workgroups' fp64 partials added in index order by a second launch; no float atomics:
+ * two calls give the same bits.  Scratch: 8 ceil(P / 256) + 256 bytes. */
+int gs4d_mcmc_reg_grad(int P, const float *opacity_raw, const float *scaling_raw, float w_opacity, float w_scale,
+                       float *value, float *grad_opacity, float *grad_scaling, gs4d_alloc_fn scratch_alloc,
+                       void *scratch_ctx, void *stream);
+/* Rows rows[0 .. n-1] of `count` float tensors (P, width) set to zero in one launch (the Adam moments of relocated
+ * and grown rows).  Duplicates are fine; an index outside [0, P) is skipped.  Status 1 for a NULL batch, count
+ * outside 0 .. GS4D_ROWS_MAX_TENSORS, negative P or n, or with work to do a NULL row list, a NULL tensor or a width
+ * outside 1 .. 2^20. */
+typedef struct {
+    float *data;
+    int64_t width;
+} gs4d_zero_rows_tensor;
+typedef struct {
+    int count;
+    int64_t P, n;
+    const int32_t *rows;
+    gs4d_zero_rows_tensor t[GS4D_ROWS_MAX_TENSORS];
+} gs4d_zero_rows_batch;
+int gs4d_mcmc_zero_rows(const gs4d_zero_rows_batch *batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
